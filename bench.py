@@ -12,7 +12,10 @@ single-batch semantics via ShardedGE2E), gradients SUM-all-reduced over RCCL.
 
 Headline line (rank 0 prints ONE JSON line): config c2 (fp32, the reference's precision) with
 N = 64 speakers PER GPU -> weak scaling; value = world * N * M * steps / max-over-ranks time.
-Side measurements in the same line:
+A plain run does only that: set-up, --warmup untimed steps, --steps timed steps, the line
+(ms_per_step = the timed seconds / --steps).  --dump-outputs DIR also writes what the last timed
+step left with its caller (loss, parameters, gradients) as DIR/<name>.npy.
+Side measurements in the same line, with --full only:
   bf16            c3: the same per-GPU workload with bf16 GEMM operands (weak scaling)
   c4              (world > 1) c3's global batch N = 64 x M = 10 split over the ranks, bf16:
                   strong scaling, value = 640 * steps / time
@@ -52,6 +55,8 @@ MI355X_BF16_MFMA_TFLOPS = 2500.0  # dense bf16 MFMA (no sparsity)
 METRIC = "embeddings/sec + GE2E steps/sec at N=64×M=10, 1/2/4/8 MI355X"
 SIDE_STEPS = 40  # timed steps of each side line at least (the headline times exactly --steps)
 DIMS = (40, 768, 3, 256)          # nmels, hidden, layers, proj (config/config.yaml)
+DUMP_MAX_ELEMS = 1 << 22          # --dump-outputs: elements kept of params / grads (16 MB of float32 each)
+DUMP_SEED = 20240
 
 
 def step_flops(B, T, F, H, P, L):
@@ -148,6 +153,29 @@ def run_steps(ctx, N, M, T, precision, steps, warmup, seed, probe=None, products
     tr.check()  # raises if a persistent recurrence timed out during the timed steps
     log(f"  {dt / steps * 1e3:.3f} ms/step")
     return dt, float(loss), host, probes, tr
+
+
+def _dump_sample(t):
+    """t flattened as float32 on the host; past DUMP_MAX_ELEMS a fixed (seeded, sorted) sample of it."""
+    a = t.detach().reshape(-1).float().cpu().numpy()
+    if a.size > DUMP_MAX_ELEMS:
+        a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def dump_outputs(path, tr, loss):
+    """--dump-outputs: what a caller of GE2ETrainer.step holds after the last timed step -- the
+    returned loss, and the parameters and gradients the step left in the modules (net and GE2E
+    w, b) -- as <path>/<name>.npy.  The inputs and the initialisation are seeded, so two builds run
+    with the same arguments can be compared array by array."""
+    os.makedirs(path, exist_ok=True)
+    n, n_pad = tr.n, tr.n_pad
+    arrays = {"loss": np.array([loss], dtype=np.float64),
+              "params": _dump_sample(tr.flat_p[:n]), "ge2e_wb": _dump_sample(tr.flat_p[n_pad:n_pad + 2]),
+              "grads": _dump_sample(tr.flat_g[:n]), "ge2e_wb_grads": _dump_sample(tr.flat_g[n_pad:n_pad + 2])}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"dumped {', '.join(arrays)} ({sum(a.nbytes for a in arrays.values()) / 1e6:.1f} MB) to {path}")
 
 
 def kstamp_us(probes):
@@ -714,6 +742,13 @@ def main():
                          "c4 = N64 M10 T160 bf16 split over the GPUs (strong scaling), c5 = N256 M10 T180 bf16 "
                          "split over the GPUs")
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every side measurement (probed roofline runs, forward-only, "
+                         "bf16 / rank shapes / bf16x6, isolated kernels, d-vector, vendor, drop-in loop and CPU "
+                         "baselines); the --no-* and --fwd-steps options select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned and updated (loss, "
+                         "parameters, gradients) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -743,11 +778,10 @@ def main():
     # fp32: the persistent recurrences where the library picks them (c2: 240 of 256 CUs), else
     # the per-step kernels with their in-kernel stamps
     f32_persist = dtype == "f32" and bool(_svlib().sv_lstm_f32_persist_ok(B, H, 0))
-    # the step time without timing probes (each probe event record idles the GPU ~6 us between two
-    # kernels: 12 records per c2 step), then the same steps again with the probes for the roofline
+    # the step time without timing probes (--full runs the same steps again with the probes)
     dt, loss, host, _, tr = run_steps(ctx, N, M, T, dtype, args.steps, args.warmup, 1235)
-    dt_probed, _, _, probes, _ = run_steps(ctx, N, M, T, dtype, args.steps, 1, 1235,
-                                           probe="bwd_chunks" if dtype == "f32" and not f32_persist else "fwd_bwd")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr, loss)
     ms_step = dt / args.steps * 1e3
     fwd_fl, st_fl = step_flops(B, T, F, H, P, L)
     peak = MI355X_FP32_MFMA_TFLOPS if dtype == "f32" else MI355X_BF16_MFMA_TFLOPS
@@ -772,11 +806,32 @@ def main():
                    "parallelism": f"dp{world} (speaker-sharded GE2E, RCCL grad all-reduce)"},
         "steps_per_sec": round(args.steps / dt, 4),
         "host_enqueue_ms_per_step": round(host / args.steps * 1e3, 3),
-        "probed_ms_per_step": round(dt_probed / args.steps * 1e3, 3),
         "loss": round(loss, 5),
         "step_tflops_per_gpu": round(st_fl / (ms_step * 1e-3) / 1e12, 2),
         "step_mfma_frac": round(st_fl / (ms_step * 1e-3) / 1e12 / peak, 4),
     }
+    if args.full:
+        full_measurements(args, ctx, out, tr, dt, N, M, T, dtype, strong, f32_persist)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_measurements(args, ctx, out, tr, dt, N, M, T, dtype, strong, f32_persist):
+    """--full: everything beside the headline (module docstring), added to the result line `out`.
+    tr: the headline run's trainer; dt: its timed seconds."""
+    world, rank, dev = ctx.world, ctx.rank, ctx.dev
+    F, H, L, P = DIMS
+    B = N * M
+    ms_step = dt / args.steps * 1e3
+    emb_total = world * B
+    # the headline's steps again with timing probes for the roofline (each probe event record idles
+    # the GPU ~6 us between two kernels: 12 records per c2 step, so the headline runs without them)
+    dt_probed, _, _, probes, _ = run_steps(ctx, N, M, T, dtype, args.steps, 1, 1235,
+                                           probe="bwd_chunks" if dtype == "f32" and not f32_persist else "fwd_bwd")
+    out["probed_ms_per_step"] = round(dt_probed / args.steps * 1e3, 3)
     if f32_persist:
         fl = 2.0 * B * T * H * 4 * H
         out["roofline"] = roofline_entry(
@@ -919,11 +974,6 @@ def main():
         out["dropin_loop"]["vs_fused_trainer"] = round(out["dropin_loop"]["ms_per_step"] / ms_step, 4)
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(N, M, T)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -42,7 +42,7 @@ def line(f, what, d, bench_us, flops):
 
 B, T, H = 640, 160, 768
 with open(os.path.join(prof, f"{tag}_roofline_check.txt"), "w") as f:
-    f.write("rocprofv3 kernel traces of `bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-vendor --no-bf16 "
+    f.write("rocprofv3 kernel traces of `bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-vendor --no-bf16 "
             "--fwd-steps 1` (f32, c2) and `... --dtype bf16` (c3) against the bench line of the same tree\n")
     rf = pf["f32"]["roofline"]
     if rf["kernel"].startswith("lstm_persist_bwd_f32_h2_kernel"):
