@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SV_ABI_VERSION 11
+#define SV_ABI_VERSION 12
 int sv_abi_version(void);
 
 /* ---- fp32 product modes (`products` argument of sv_gemm_f32 / sv_lstm_stack_fwd / _bwd; every
@@ -62,9 +62,9 @@ int sv_abi_version(void);
  *                       idle for ~6 us between two kernels); the per-step schedule, whose side
  *                       streams synchronise through the events, ignores it.
  * bf16 stack backward only:
- *   SV_SCHED_WT_READY   (ABI v10) the workspace already holds the bf16 weight transposes, written by
- *                       sv_lstm_weights_bf16 (below) from the same weights into the same workspace:
- *                       no transpose launch (the fp32 backward ignores it).
+ *   SV_SCHED_WT_READY   the `wt` buffer is already filled: sv_lstm_weights_bf16 / sv_lstm_prep_bf16
+ *                       (below) wrote the bf16 weight transposes into it from the same weights, so
+ *                       the backward launches no transposes (the fp32 backward ignores it).
  *   SV_SCHED_CNT_READY  (ABI v11) the sync block's backward counter channels are still as the last
  *                       bf16 stack forward on it left them (it zeroes them) -- no backward has run
  *                       on the block since: the persistent / wavefront backward launches no
@@ -270,18 +270,22 @@ int sv_transpose_cast_bf16(const float* src, long ld_src, int R, int C, sv_bf16*
 /* (ABI v10) the bf16 stack's input in one launch: frames x [B,T,F] (F <= 64) -> x_bf [T,B,F] and,
  * if xT != NULL, xT [F][T*Bp] (column t*Bp + b = x[b,t,:], columns b in [B, Bp) zero) */
 int sv_frames_to_bf16(const float* x, int B, int T, int F, sv_bf16* x_bf, sv_bf16* xT, int Bp, hipStream_t stream);
-/* (ABI v10) every layer's bf16 weights in one launch, each fp32 weight read once: w_ih_bf[l] /
- * w_hh_bf[l] = bf16(w_ih[l]) / bf16(w_hh[l]) (row-major, the stack forward's operands) and, if
- * bwd_workspace != NULL (sv_lstm_bwd_workspace(SV_DTYPE_BF16, L, T, B, F, H) bytes), the bf16
- * transposes the stack backward reads, inside that workspace: pass it to sv_lstm_bwd with
- * SV_SCHED_WT_READY and the backward launches no transposes. */
-int sv_lstm_weights_bf16(int L, int T, int B, int F, int H, const float* const* w_ih, const float* const* w_hh,
-                         sv_bf16* const* w_ih_bf, sv_bf16* const* w_hh_bf, void* bwd_workspace, hipStream_t stream);
-/* (ABI v11) sv_frames_to_bf16 (frames x [B,T,F] -> x_bf, xT) and sv_lstm_weights_bf16 in ONE launch:
- * the bf16 stack forward's whole operand preparation. */
+/* `wt`: the buffer of bf16 weight transposes that the bf16 stack backward reads -- W_hh^T [H][4H]
+ * of every layer and W_ih^T of layers >= 1 (rows padded by the library), each piece 256-byte
+ * aligned.  sv_lstm_wt_bf16_size bytes (independent of T and B; 0 for a non-positive argument);
+ * the caller allocates it 256-byte aligned, the library alone knows its layout. */
+size_t sv_lstm_wt_bf16_size(int L, int F, int H);
+/* every layer's bf16 weights in one launch, each fp32 weight read once: w_ih_bf[l] / w_hh_bf[l] =
+ * bf16(w_ih[l]) / bf16(w_hh[l]) (row-major, the stack forward's operands) and, if wt != NULL, the
+ * transposes into wt: pass it to sv_lstm_bwd with SV_SCHED_WT_READY and the backward launches no
+ * transposes.  wt == NULL: the row-major copies only. */
+int sv_lstm_weights_bf16(int L, int F, int H, const float* const* w_ih, const float* const* w_hh,
+                         sv_bf16* const* w_ih_bf, sv_bf16* const* w_hh_bf, void* wt, hipStream_t stream);
+/* sv_frames_to_bf16 (frames x [B,T,F] -> x_bf, xT) and sv_lstm_weights_bf16 in ONE launch: the bf16
+ * stack forward's whole operand preparation. */
 int sv_lstm_prep_bf16(int L, int T, int B, int F, int H, const float* x, sv_bf16* x_bf, sv_bf16* xT, int Bp,
                       const float* const* w_ih, const float* const* w_hh, sv_bf16* const* w_ih_bf,
-                      sv_bf16* const* w_hh_bf, void* bwd_workspace, hipStream_t stream);
+                      sv_bf16* const* w_hh_bf, void* wt, hipStream_t stream);
 /* x_bf [T,B,F]; writes gates (bf16), c_tm/h_tm (fp32) plus h_bf [T+1,B,H] and hT [H,(T+1)Bp] (bf16) */
 int sv_lstm_layer_fwd_bf16(const sv_bf16* x_bf, int T, int B, int F, int H, const sv_bf16* w_ih_bf,
                            const sv_bf16* w_hh_bf, const float* b_ih, const float* b_hh, sv_bf16* gates, float* c_tm,
@@ -305,17 +309,20 @@ int sv_lstm_layer_bwd_bf16(int T, int B, int F, int H, const sv_bf16* xT_bf, lon
                            float* dw_ih, float* dw_hh, float* db_ih, float* db_hh, float* workspace,
                            hipStream_t stream);
 
-/* stack backward in bf16 under `schedule` (as sv_lstm_stack_bwd, L side streams; fp32 master
- * weights are transpose-cast per call; dg/dgT per layer bf16).  probe: as the bf16 stack
- * forward's, around each layer's persistent backward recurrence. */
+/* stack backward in bf16 under `schedule` (as sv_lstm_stack_bwd, L side streams; dg/dgT per layer
+ * bf16).  workspace: sv_lstm_stack_bwd_bf16_workspace bytes of scratch (per-layer GEMM scratch and
+ * the recurrences' hand-off; nothing in it outlives the call).  wt (required, sv_lstm_wt_bf16_size
+ * bytes): the bf16 weight transposes -- already filled under SV_SCHED_WT_READY, else the backward
+ * fills it from the fp32 master weights w_ih / w_hh.  probe: as the bf16 stack forward's, around
+ * each layer's persistent backward recurrence. */
 size_t sv_lstm_stack_bwd_bf16_workspace(int L, int T, int B, int F, int H);
 int sv_lstm_stack_bwd_bf16(int L, int T, int B, int F, int H, const sv_bf16* const* xT, const long* ld_xT,
                            const float* const* w_ih, const float* const* w_hh, const sv_bf16* const* gates,
                            const float* const* c_tm, const sv_bf16* const* hT, const float* dh_last,
                            sv_bf16* const* dg, sv_bf16* const* dgT, float* const* dx, float* const* dw_ih,
-                           float* const* dw_hh, float* const* db_ih, float* const* db_hh, void* workspace, int chunk,
-                           hipStream_t main, const hipStream_t* side, hipEvent_t* ev, void* sync, hipEvent_t* probe,
-                           int schedule);
+                           float* const* dw_hh, float* const* db_ih, float* const* db_hh, void* workspace, void* wt,
+                           int chunk, hipStream_t main, const hipStream_t* side, hipEvent_t* ev, void* sync,
+                           hipEvent_t* probe, int schedule);
 
 /* ---- dtype-enum form of the stack entry points (SURVEY.md §8 b: `lstm_fwd` = K1 + K2 and
  * `lstm_bwd` = K3 + K4 with a dtype argument; replaces the nn.LSTM forward / autograd backward at
@@ -324,7 +331,8 @@ int sv_lstm_stack_bwd_bf16(int L, int T, int B, int F, int H, const sv_bf16* con
  *                     (pass NULL);
  *   SV_DTYPE_BF16  -> sv_lstm_stack_fwd_bf16 / _bwd_bf16: the `void` operands are sv_bf16
  *                     (x, w_ih, w_hh, gates, h_bf, hT; in the backward xT, gates, hT, dg, dgT);
- *                     `products` and `kstamp` are ignored (pass 0 / NULL).
+ *                     `products` and `kstamp` are ignored (pass 0 / NULL); the backward's `wt`
+ *                     (sv_lstm_wt_bf16_size bytes) is required (NULL: SV_EARG).  fp32 ignores `wt`.
  * Every other argument means what it means in the dtype-specific entry point; the backward takes
  * the fp32 master weights in both dtypes.  An unknown dtype returns SV_EARG. */
 #define SV_DTYPE_F32 0
@@ -339,8 +347,8 @@ int sv_lstm_bwd(int dtype, int L, int T, int B, int F, int H, const void* const*
                 const float* const* w_ih, const float* const* w_hh, const void* const* gates, const float* const* c_tm,
                 const void* const* hT, const float* dh_last, void* const* dg, void* const* dgT, float* const* dx,
                 float* const* dw_ih, float* const* dw_hh, float* const* db_ih, float* const* db_hh, void* workspace,
-                int chunk, hipStream_t main, const hipStream_t* side, hipEvent_t* ev, int products, hipEvent_t* probe,
-                unsigned long long* kstamp, int schedule, void* sync);
+                void* wt, int chunk, hipStream_t main, const hipStream_t* side, hipEvent_t* ev, int products,
+                hipEvent_t* probe, unsigned long long* kstamp, int schedule, void* sync);
 
 /* ---- persistent recurrences (one launch per layer for all T; sv_persist.hip).  The bf16 stack
  * forward uses them (by default when H = 768: W_hh held in registers) when the grid is

@@ -44,9 +44,9 @@ extern "C" int sv_lstm_bwd(int dtype, int L, int T, int B, int F, int H, const v
                            const float* const* w_ih, const float* const* w_hh, const void* const* gates,
                            const float* const* c_tm, const void* const* hT, const float* dh_last, void* const* dg,
                            void* const* dgT, float* const* dx, float* const* dw_ih, float* const* dw_hh,
-                           float* const* db_ih, float* const* db_hh, void* workspace, int chunk, hipStream_t main,
-                           const hipStream_t* side, hipEvent_t* ev, int products, hipEvent_t* probe,
-                           unsigned long long* kstamp, int schedule, void* sync) {
+                           float* const* db_ih, float* const* db_hh, void* workspace, void* wt, int chunk,
+                           hipStream_t main, const hipStream_t* side, hipEvent_t* ev, int products,
+                           hipEvent_t* probe, unsigned long long* kstamp, int schedule, void* sync) {
   switch (dtype) {
     case SV_DTYPE_F32:
       return sv_lstm_stack_bwd(L, T, B, F, H, reinterpret_cast<const float* const*>(xT), ld_xT, w_ih, w_hh,
@@ -60,7 +60,8 @@ extern "C" int sv_lstm_bwd(int dtype, int L, int T, int B, int F, int H, const v
                                     reinterpret_cast<const sv_bf16* const*>(gates), c_tm,
                                     reinterpret_cast<const sv_bf16* const*>(hT), dh_last,
                                     reinterpret_cast<sv_bf16* const*>(dg), reinterpret_cast<sv_bf16* const*>(dgT), dx,
-                                    dw_ih, dw_hh, db_ih, db_hh, workspace, chunk, main, side, ev, sync, probe, schedule);
+                                    dw_ih, dw_hh, db_ih, db_hh, workspace, wt, chunk, main, side, ev, sync, probe,
+                                    schedule);
     default:
       return SV_EARG;
   }

@@ -1227,7 +1227,6 @@ extern "C" int sv_lstm_stack_fwd_bf16(int L, int T, int B, int F, int H, const b
 namespace {
 struct BBwdWs {
   float *dcf0, *dcf1, *gws;
-  bf16_t *whhT, *wihT;
   size_t gbytes, total;  // gws bytes; the region's
 };
 BBwdWs carve_bbwd(char* base, int T, int B, int F, int H) {
@@ -1240,8 +1239,6 @@ BBwdWs carve_bbwd(char* base, int T, int B, int F, int H) {
   };
   w.dcf0 = (float*)take((size_t)B * H * 4);
   w.dcf1 = (float*)take((size_t)B * H * 4);
-  w.whhT = (bf16_t*)take((size_t)4 * H * H * 2);
-  w.wihT = (bf16_t*)take((size_t)bf16_wiht_ld(H) * F * 2);
   const int TBp = T * ((B + 7) & ~7);
   size_t g = sv_gemm_bf16_workspace(4 * H, H, TBp);
   g = std::max(g, sv_gemm_bf16_workspace(4 * H, F, TBp));
@@ -1254,11 +1251,29 @@ BBwdWs carve_bbwd(char* base, int T, int B, int F, int H) {
 }
 }  // namespace
 
-// L per-layer regions, then the persistent backward's hand-off scratch (shared by the layers,
-// whose recurrences run one after another)
-// W_hh^T of every layer and W_ih^T of layers >= 1 (bf16 [K, 4H]) in one or two launches
-static int wbf_transposes(int L, int F, int H, const float* const* w_ih, const float* const* w_hh,
-                          const bf16_t* const* whhT, const bf16_t* const* wihT, hipStream_t s) {
+// The bf16 weight transposes the stack backward reads live in a buffer of their own, `wt`
+// (sv_lstm_wt_bf16_size bytes; independent of T and B): W_hh^T [H][4H] of every layer and W_ih^T
+// [H][bf16_wiht_ld(H)] of layers >= 1, each piece 256-byte aligned.  wt_layer is the only place
+// that knows the layout: layer l's two pointers (NULL where wt is NULL; wihT NULL for layer 0)
+// and the offset at which the layer ends.
+struct WtLayer {
+  bf16_t *whhT, *wihT;
+  size_t end;
+};
+static WtLayer wt_layer(void* wt, int l, int H) {
+  const size_t hh = ((size_t)4 * H * H * 2 + 255) & ~size_t(255);
+  const size_t ih = ((size_t)bf16_wiht_ld(H) * H * 2 + 255) & ~size_t(255);
+  const size_t off = l ? hh + (size_t)(l - 1) * (hh + ih) : 0;
+  char* p = wt ? (char*)wt + off : nullptr;
+  return {(bf16_t*)p, (l && p) ? (bf16_t*)(p + hh) : nullptr, off + hh + (l ? ih : 0)};
+}
+extern "C" size_t sv_lstm_wt_bf16_size(int L, int F, int H) {
+  return (L <= 0 || F <= 0 || H <= 0) ? 0 : wt_layer(nullptr, L - 1, H).end;
+}
+
+// W_hh^T of every layer and W_ih^T of layers >= 1 (bf16 [K, 4H]) into wt, in one or two launches
+static int wbf_transposes(int L, int F, int H, const float* const* w_ih, const float* const* w_hh, void* wt,
+                          hipStream_t s) {
   const float* src[8];
   bf16_t* dst[8];
   long lds[8], ldd[8];
@@ -1269,12 +1284,13 @@ static int wbf_transposes(int L, int F, int H, const float* const* w_ih, const f
     return rc;
   };
   for (int l = 0; l < L; ++l) {
+    const WtLayer w = wt_layer(wt, l, H);
     for (int m = 0; m < (l > 0 ? 2 : 1); ++m) {
       if (n == 8)
         if (int rc = flush()) return rc;
       const int K = m == 0 ? H : (l == 0 ? F : H);
       src[n] = m == 0 ? w_hh[l] : w_ih[l];
-      dst[n] = const_cast<bf16_t*>(m == 0 ? whhT[l] : wihT[l]);
+      dst[n] = m == 0 ? w.whhT : w.wihT;
       lds[n] = K;
       ldd[n] = m == 0 ? 4L * H : bf16_wiht_ld(H);
       R[n] = 4 * H;
@@ -1285,44 +1301,23 @@ static int wbf_transposes(int L, int F, int H, const float* const* w_ih, const f
   return flush();
 }
 
-// ABI v10: every layer's bf16 weights in one launch (transpose_cast_batch_kernel, each fp32 weight
-// read once): the forward's row-major operands w_ih_bf / w_hh_bf and, when bwd_workspace is given
-// (a stack-backward workspace, sv_lstm_bwd_workspace(SV_DTYPE_BF16, ...)), the transposes the stack
-// backward reads -- W_hh^T of every layer, W_ih^T of layers >= 1 -- in that workspace's per-layer
-// regions, so that sv_lstm_bwd with SV_SCHED_WT_READY on the same workspace launches none (at the
-// c4 rank shape: the forward's cast and the backward's transposes, 13 + 20 us, read every weight
-// twice)
-static int weights_bf16(int L, int T, int B, int F, int H, const float* const* w_ih, const float* const* w_hh,
-                        bf16_t* const* w_ih_bf, bf16_t* const* w_hh_bf, void* bwd_workspace, hipStream_t stream,
-                        const FramesArgs* frames);
-extern "C" int sv_lstm_weights_bf16(int L, int T, int B, int F, int H, const float* const* w_ih,
-                                    const float* const* w_hh, bf16_t* const* w_ih_bf, bf16_t* const* w_hh_bf,
-                                    void* bwd_workspace, hipStream_t stream) {
-  return weights_bf16(L, T, B, F, H, w_ih, w_hh, w_ih_bf, w_hh_bf, bwd_workspace, stream, nullptr);
-}
-// ABI v11: sv_frames_to_bf16 and sv_lstm_weights_bf16 as ONE launch (the frames' workgroups beside
-// the weight tiles: at the c4 rank shape 10 + 17 us one after the other)
-extern "C" int sv_lstm_prep_bf16(int L, int T, int B, int F, int H, const float* x, bf16_t* x_bf, bf16_t* xT, int Bp,
-                                 const float* const* w_ih, const float* const* w_hh, bf16_t* const* w_ih_bf,
-                                 bf16_t* const* w_hh_bf, void* bwd_workspace, hipStream_t stream) {
-  if (!x || !x_bf || F > 64 || (xT && Bp < B)) return SV_EARG;
-  const FramesArgs fa = frames_args(x, B, T, F, x_bf, xT, Bp);
-  return weights_bf16(L, T, B, F, H, w_ih, w_hh, w_ih_bf, w_hh_bf, bwd_workspace, stream, &fa);
-}
-static int weights_bf16(int L, int T, int B, int F, int H, const float* const* w_ih, const float* const* w_hh,
-                        bf16_t* const* w_ih_bf, bf16_t* const* w_hh_bf, void* bwd_workspace, hipStream_t stream,
+// Every layer's bf16 weights in one launch (transpose_cast_batch_kernel, each fp32 weight read
+// once): the forward's row-major operands w_ih_bf / w_hh_bf and, when wt is given, the transposes
+// the stack backward reads (wt_layer), so that sv_lstm_bwd with SV_SCHED_WT_READY on the same wt
+// launches none (at the c4 rank shape: the forward's cast and the backward's transposes, 13 + 20 us,
+// read every weight twice).  frames: sv_frames_to_bf16's work in the same (last) launch.
+static int weights_bf16(int L, int F, int H, const float* const* w_ih, const float* const* w_hh,
+                        bf16_t* const* w_ih_bf, bf16_t* const* w_hh_bf, void* wt, hipStream_t stream,
                         const FramesArgs* frames) {
-  if (L <= 0 || !w_ih || !w_hh || !w_ih_bf || !w_hh_bf) return SV_EARG;
-  if (T <= 0 || B <= 0 || F <= 0 || H <= 0 || F % 8 || H % 8) return SV_ESHAPE;
-  const size_t per = carve_bbwd(nullptr, T, B, std::max(F, H), H).total;
+  if (L <= 0 || !w_ih || !w_hh || !w_ih_bf || !w_hh_bf || ((uintptr_t)wt & 255)) return SV_EARG;
+  if (F <= 0 || H <= 0 || F % 8 || H % 8) return SV_ESHAPE;
   const float* src[8];
   bf16_t *dst[8], *dstr[8];
   long lds[8], ldd[8];
   int R[8], C[8], n = 0;
   for (int l = 0; l < L; ++l) {
     if (!w_ih[l] || !w_hh[l] || !w_ih_bf[l] || !w_hh_bf[l]) return SV_EARG;
-    BBwdWs ws{};
-    if (bwd_workspace) ws = carve_bbwd((char*)bwd_workspace + per * l, T, B, std::max(F, H), H);
+    const WtLayer w = wt_layer(wt, l, H);
     for (int m = 0; m < 2; ++m) {  // m = 0: W_ih [4H][F_l], m = 1: W_hh [4H][H]
       if (n == 8) {
         if (int rc = transpose_cast_bf16_batch(n, src, lds, R, C, dst, ldd, stream, dstr)) return rc;
@@ -1331,7 +1326,7 @@ static int weights_bf16(int L, int T, int B, int F, int H, const float* const* w
       const int K = (m == 0 && l == 0) ? F : H;
       src[n] = m == 0 ? w_ih[l] : w_hh[l];
       dstr[n] = m == 0 ? w_ih_bf[l] : w_hh_bf[l];
-      dst[n] = !bwd_workspace ? nullptr : m == 1 ? ws.whhT : (l > 0 ? ws.wihT : nullptr);
+      dst[n] = m == 1 ? w.whhT : w.wihT;
       ldd[n] = m == 1 ? 4L * H : bf16_wiht_ld(H);
       lds[n] = K;
       R[n] = 4 * H;
@@ -1341,12 +1336,26 @@ static int weights_bf16(int L, int T, int B, int F, int H, const float* const* w
   }
   return transpose_cast_bf16_batch(n, src, lds, R, C, dst, ldd, stream, dstr, frames);  // frames: the last launch
 }
+extern "C" int sv_lstm_weights_bf16(int L, int F, int H, const float* const* w_ih, const float* const* w_hh,
+                                    bf16_t* const* w_ih_bf, bf16_t* const* w_hh_bf, void* wt, hipStream_t stream) {
+  return weights_bf16(L, F, H, w_ih, w_hh, w_ih_bf, w_hh_bf, wt, stream, nullptr);
+}
+// sv_frames_to_bf16 and sv_lstm_weights_bf16 as ONE launch (the frames' workgroups beside the weight
+// tiles: at the c4 rank shape 10 + 17 us one after the other)
+extern "C" int sv_lstm_prep_bf16(int L, int T, int B, int F, int H, const float* x, bf16_t* x_bf, bf16_t* xT, int Bp,
+                                 const float* const* w_ih, const float* const* w_hh, bf16_t* const* w_ih_bf,
+                                 bf16_t* const* w_hh_bf, void* wt, hipStream_t stream) {
+  if (!x || !x_bf || F > 64 || (xT && Bp < B)) return SV_EARG;
+  if (T <= 0 || B <= 0) return SV_ESHAPE;
+  const FramesArgs fa = frames_args(x, B, T, F, x_bf, xT, Bp);
+  return weights_bf16(L, F, H, w_ih, w_hh, w_ih_bf, w_hh_bf, wt, stream, &fa);
+}
 
 #ifndef SV_PERSIST_FULLK
 #define SV_PERSIST_FULLK 1  // the persistent schedule's weight gradients as one whole-K launch (A/B)
 #endif
-// the hand-off scratch shared by the layers (persistent or wavefront backward), behind the L
-// per-layer regions
+// the stack backward's workspace: L per-layer regions (carve_bbwd), then the hand-off scratch shared
+// by the layers (persistent or wavefront backward; the recurrences run one after another)
 static size_t bbwd_scratch(int L, int T, int B, int H) {
   size_t scratch = sv_persist_bwd_fits(B, H, 1 << 30) ? sv_persist_bwd_scratch(T, B, H) : 0;
   if (sv_wave_bwd_fits(L, B, H, 1 << 30)) scratch = std::max(scratch, sv_wave_bwd_scratch(L, T, B, H));
@@ -1357,252 +1366,310 @@ extern "C" size_t sv_lstm_stack_bwd_bf16_workspace(int L, int T, int B, int F, i
   return per + bbwd_scratch(L, T, B, H);
 }
 
+namespace {
+// sv_lstm_stack_bwd_bf16's validated arguments (named as in its signature) and the sizes derived
+// from them, shared by its three schedules
+struct BBwdArgs {
+  int L, T, B, F, H;
+  const bf16_t* const* xT;
+  const long* ld_xT;
+  const float* const* w_ih;
+  const float* const* w_hh;
+  const bf16_t* const* gates;
+  const float* const* c_tm;
+  const bf16_t* const* hT;
+  const float* dh_last;
+  bf16_t* const* dg;
+  bf16_t* const* dgT;
+  float* const* dx;
+  float* const* dw_ih;
+  float* const* dw_hh;
+  float* const* db_ih;
+  float* const* db_hh;
+  char* workspace;
+  void* wt;
+  int chunk;
+  hipStream_t main;
+  const hipStream_t* side;
+  hipEvent_t* ev;
+  unsigned* sync;
+  hipEvent_t* probe;
+  int nch;       // chunks of `chunk` timesteps
+  long BH, BG;   // elements of one timestep of h / of the gates
+  int Bp, TBp;   // B rounded up to 8; T * Bp
+  long ldhT;     // row stride of hT
+  size_t per;    // bytes of one per-layer workspace region
+  // the per-layer completion events (a caller's gradient buckets wait on them) of the persistent and
+  // wavefront schedules; SV_SCHED_NO_EVENTS: nobody waits, record none (each record idles the GPU)
+  bool evs;
+  bool wt_ready;  // SV_SCHED_WT_READY: the caller filled wt (sv_lstm_weights_bf16): no transpose launches
+  // SV_SCHED_CNT_READY: the stack forward zeroed the backward's counter channels and no backward
+  // has used this sync block since (the caller tracks that): no zeroing launches here
+  bool cnt_ready;
+  BBwdWs region(int l) const { return carve_bbwd(workspace + per * l, T, B, std::max(F, H), H); }
+  char* scratch() const { return workspace + per * L; }  // the recurrences' hand-off scratch
+};
+
+// every layer's whole-K weight-gradient tiles in one launch where they fit one round of the CUs
+// (gemm_bf16_8qf_kernel; layer 0's N = F dW_ih after it on the narrow kernel), the split form
+// (first pieces on the CUs the tiles leave free, their flags on channel SV_BWD_CH0 + WB_L) where
+// at least 8 CUs are left over and the partials fit the GEMM scratch
+bool plan_fullk(const BBwdArgs& a, G8Full& f, int& fP) {
+  const int L = a.L, F = a.F, H = a.H, TBp = a.TBp;
+  const int cus = sv_stream_cus(a.main);
+  f = G8Full{};
+  fP = 0;
+  if (!(L == WB_L && gemm256_ok(4 * H, H, TBp) && TBp % 8 == 0 && a.ldhT % 8 == 0)) return false;
+  bool fullk = true;
+  f.K = TBp;
+  for (int l = 0; l < L; ++l) {
+    // upper layers: dW_ih beside dW_hh (input width H, 3 column tiles); layer 0 too (x0 tile):
+    // its F <= 256 columns as one partial column tile (x^T rows clamped, F columns stored) --
+    // the narrow GEMM after the launch re-read all of dG^T_0 for them (c5 rank 76 + 10 us)
+    const bool x0 = l == 0 && F <= G256_BM && F % 4 == 0;
+    const bool dual = l > 0 || x0;
+    G8FLayer& fl = f.lay[l];
+    fl.A = a.dgT[l];
+    fl.lda = TBp;
+    fl.B = a.hT[l];
+    fl.ldb = a.ldhT;
+    fl.B2 = dual ? a.xT[l] : nullptr;
+    fl.ldb2 = dual ? a.ld_xT[l] : 0;
+    fl.C1 = a.dw_hh[l];
+    fl.ldc1 = H;
+    fl.C2 = dual ? a.dw_ih[l] : nullptr;
+    fl.ldc2 = l > 0 ? H : F;
+    fl.n1 = H;
+    fl.N = l > 0 ? 2 * H : x0 ? H + G256_BM : H;
+    fl.f2 = x0 ? F : 0;
+    fl.tiles = (4 * H / G256_BM) * (fl.N / G256_BM);
+    fP += fl.tiles;
+    if (((uintptr_t)a.dgT[l] | (uintptr_t)a.hT[l] | (uintptr_t)a.dw_hh[l]) & 15) fullk = false;
+    if (dual && ((((uintptr_t)a.xT[l] | (uintptr_t)a.dw_ih[l]) & 15) || a.ld_xT[l] % 8 || fl.ldc2 % 4)) fullk = false;
+  }
+  fullk = fullk && fP <= cus;
+  const BBwdWs wsp = a.region(L - 1);
+  const int KT = TBp / G256_BK;
+  f.nsw = fullk ? (cus - fP) / 8 * 8 : 0;
+  if (f.nsw > 0) {
+    const int per_wg = (fP + f.nsw - 1) / f.nsw;  // first pieces per workgroup
+    f.S = KT / (per_wg + 1) - 2;    // (their stores and prologues: a little less)
+  }
+  if (f.nsw <= 0 || f.S < 4 || (size_t)fP * G256_BM * G256_BM * 4 > wsp.gbytes) f.nsw = f.S = 0;
+  if (f.S > 0) {
+    f.part = wsp.gws;
+    f.flag = a.sync + SV_SYNC_CNT + (size_t)(SV_BWD_CH0 + WB_L) * SV_PCNT_ROWS * SV_PCNT_STRIDE;
+    f.status = a.sync;
+    f.limit = sv_persist_limit();
+  }
+  return fullk;
+}
+
+// the whole-K launch plan_fullk planned, then layer 0's dW_ih and the layers' completion events
+int run_fullk(const BBwdArgs& a, const G8Full& f, int fP) {
+  const int L = a.L, F = a.F, H = a.H, TBp = a.TBp;
+  hipError_t e;
+  hipLaunchKernelGGL(gemm_bf16_8qf_kernel, dim3(f.nsw + fP + dbfin_blocks(f.fin, 512)), dim3(512), G256_LDS, a.main, f);
+  SV_LAUNCH_CHECK();
+  for (int l = L - 1; l >= 1 && a.evs; --l)
+    if ((e = hipEventRecord(a.ev[L * a.nch + l], a.main)) != hipSuccess) return (int)e;
+  if (!f.lay[0].f2) {  // layer 0's dW_ih (F > 256) on its own
+    if (int rc = sv_gemm_bf16(4 * H, F, TBp, a.dgT[0], TBp, a.xT[0], a.ld_xT[0], a.dw_ih[0], F, nullptr, nullptr, 0.f,
+                              a.region(0).gws, a.main))
+      return rc;
+  }
+  if (a.evs && (e = hipEventRecord(a.ev[L * a.nch], a.main)) != hipSuccess) return (int)e;
+  return SV_OK;
+}
+
+// layer-wavefront schedule: every layer's recurrence and upstream gradient dx in one launch
+// (sv_persist3.hip, no dx GEMMs; bias gradients summed in the kernel), then per layer the
+// weight gradients on `main`
+int bwd_wave(const BBwdArgs& a) {
+  const int L = a.L, T = a.T, B = a.B, F = a.F, H = a.H, TBp = a.TBp;
+  hipError_t e;
+  const bf16_t* whhT_l[WB_L];
+  const bf16_t* wihT_l[WB_L];
+  for (int l = 0; l < L; ++l) {
+    const WtLayer w = wt_layer(a.wt, l, H);
+    whhT_l[l] = w.whhT;
+    wihT_l[l] = w.wihT;
+  }
+  int rc = a.wt_ready ? 0 : wbf_transposes(L, F, H, a.w_ih, a.w_hh, a.wt, a.main);
+  if (rc) return rc;
+  G8Full f;
+  int fP;
+  const bool fullk = plan_fullk(a, f, fP);
+  // with the whole-K launch after it, the bias finalize rides on that launch (G8Full::fin)
+  rc = sv_wave_bwd_bf16(L, T, B, H, whhT_l, wihT_l, a.gates, a.c_tm, a.dh_last, a.dx, a.dgT, a.scratch(), a.sync,
+                        a.main, a.db_ih, a.db_hh, a.probe ? a.probe[0] : nullptr, a.probe ? a.probe[1] : nullptr,
+                        bf16_wiht_ld(H), f.S > 0 ? fP : 0, SV_BWD_CH0, a.cnt_ready, fullk ? &f.fin : nullptr);
+  if (rc) return rc;
+  if (fullk) return run_fullk(a, f, fP);
+  for (int l = L - 1; l >= 0; --l) {
+    const int Fl = l == 0 ? F : H;
+    if ((rc = sv_gemm_bf16_dual(4 * H, H, Fl, TBp, a.dgT[l], TBp, a.hT[l], a.ldhT, a.dw_hh[l], H, a.xT[l], a.ld_xT[l],
+                                a.dw_ih[l], Fl, a.region(l).gws, a.main)))
+      return rc;
+    // layer l's gradients are complete: its all-reduce bucket (grad_ready) overlaps the lower
+    // layers' weight-gradient GEMMs (the recurrences are all done)
+    if (a.evs && (e = hipEventRecord(a.ev[L * a.nch + l], a.main)) != hipSuccess) return (int)e;
+  }
+  return SV_OK;
+}
+
+// persistent schedule on `main`: per layer (top first) the whole-T recurrence in one launch
+// (sv_persist.hip; bias gradients summed in the kernel), the whole-T dx GEMM straight from its
+// fragment-order hand-off, then the layer's weight gradients (measured: on a side stream
+// beside the next layer's recurrence 16.8 vs 16.6 ms at c3 -- the GEMM workgroups contend
+// with the co-resident recurrence)
+int bwd_persist(const BBwdArgs& a) {
+  const int L = a.L, T = a.T, B = a.B, F = a.F, H = a.H, TBp = a.TBp;
+  hipStream_t main = a.main;
+  hipError_t e;
+  // every layer's W_hh^T / W_ih^T (bf16) in one launch
+  if (int rc = a.wt_ready ? 0 : wbf_transposes(L, F, H, a.w_ih, a.w_hh, a.wt, main)) return rc;
+  // the weight gradients of every layer after the last recurrence, as the layer wavefront's one
+  // whole-K launch (plan_fullk), where it applies; else per layer, split-K, after its recurrence
+  G8Full f;
+  int fP;
+  const bool fullk = SV_PERSIST_FULLK && plan_fullk(a, f, fP);
+  if (fullk && f.S > 0 && !a.cnt_ready) {  // the first pieces' flags (else zeroed by the forward)
+    if (int rc = sv_zero_counters(f.flag, 1, 0, fP, main)) return rc;
+  }
+  for (int l = L - 1; l >= 0; --l) {
+    const int Fl = l == 0 ? F : H;
+    const BBwdWs ws = a.region(l);
+    const WtLayer w = wt_layer(a.wt, l, H);
+    int rc = 0;
+    const float* up = l == L - 1 ? a.dh_last : a.dx[l + 1];
+    bf16_t* dgf = (bf16_t*)a.scratch();
+    const bool afr = l > 0 && gemm_afrag_ok(T, B, Fl, H);  // dx reads dgf: no row-major dG
+    // layer l on channel SV_BWD_CH0 + l, pre-zeroed by the forward (cnt_ready) where the layers fit
+    // the channels, else each launch zeroing its own
+    const bool own = L <= SV_SYNC_CHANNELS - SV_BWD_CH0;
+    // the bias-gradient finalize rides on the next launch (the dx GEMM; layer 0's: the whole-K
+    // weight-gradient launch), before the next recurrence reuses the partials' slots in dgf
+    DbFin fin{};
+    if ((rc = sv_persist_bwd_bf16(T, B, H, w.whhT, a.gates[l], a.c_tm[l], up, l < L - 1,
+                                  (afr || l == 0) ? nullptr : a.dg[l],  // layer 0 has no dx GEMM
+                                  a.dgT[l], dgf, main, a.sync, a.db_ih[l], a.db_hh ? a.db_hh[l] : nullptr,
+                                  a.probe ? a.probe[2 * l] : nullptr, a.probe ? a.probe[2 * l + 1] : nullptr,
+                                  SV_BWD_CH0 + (own ? l : 0), own && a.cnt_ready, &fin)))
+      return rc;
+    // the completion events of layers >= 1 (grad_ready: a caller's bucketed all-reduce) fire once
+    // the last recurrence is done, so collectives never share the device with a persistent launch
+    // (whose grid must be co-resident; a concurrent RCCL kernel would hold CUs it waits for) but
+    // overlap layer 0's weight-gradient GEMMs
+    for (int k = 1; l == 0 && k < L && a.evs && !fullk; ++k)
+      if ((e = hipEventRecord(a.ev[L * a.nch + k], main)) != hipSuccess) return (int)e;
+    if (afr) {
+      if ((rc = gemm_bf16_afrag(T, B, H, Fl, dgf, sv_persist_bm(B, H, sv_stream_cus(main)), w.wihT, bf16_wiht_ld(H),
+                                a.dx[l], Fl, ws.gws, main, fin)))
+        return rc;
+    } else if (l == 0 && fullk) {
+      f.fin = fin;
+    } else {
+      if ((rc = sv_dbfin_launch(fin, main))) return rc;
+      if (l > 0 && (rc = sv_gemm_bf16(T * B, Fl, 4 * H, a.dg[l], 4L * H, w.wihT, bf16_wiht_ld(H), a.dx[l], Fl, nullptr,
+                                      nullptr, 0.f, ws.gws, main)))
+        return rc;
+    }
+    if (fullk) continue;
+    // dW_hh and dW_ih in one pass over dG^T (falls back to two GEMMs for layer 0's F = 40)
+    rc = sv_gemm_bf16_dual(4 * H, H, Fl, TBp, a.dgT[l], TBp, a.hT[l], a.ldhT, a.dw_hh[l], H, a.xT[l], a.ld_xT[l],
+                           a.dw_ih[l], Fl, ws.gws, main);
+    if (rc) return rc;
+  }
+  if (fullk) return run_fullk(a, f, fP);
+  if (a.evs && (e = hipEventRecord(a.ev[L * a.nch], main)) != hipSuccess) return (int)e;
+  return SV_OK;
+}
+
+// per-step schedule, layer-pipelined (sv_lstm_stack_bwd, sv_lstm.hip): each layer on side[l]
+int bwd_per_step(const BBwdArgs& a) {
+  const int L = a.L, T = a.T, B = a.B, F = a.F, H = a.H, Bp = a.Bp, TBp = a.TBp, nch = a.nch;
+  const long BH = a.BH, BG = a.BG;
+  hipEvent_t* ev = a.ev;
+  bf16_t* const* dg = a.dg;
+  hipError_t e;
+  hipEvent_t ev_start = ev[L * nch + L];
+  if ((e = hipEventRecord(ev_start, a.main)) != hipSuccess) return (int)e;
+  const dim3 grid((H + BF_U - 1) / BF_U, (B + BF_BM - 1) / BF_BM);
+  for (int l = L - 1; l >= 0; --l) {
+    hipStream_t s = a.side[l];
+    const int Fl = l == 0 ? F : H;
+    const BBwdWs ws = a.region(l);
+    const WtLayer w = wt_layer(a.wt, l, H);
+    if ((e = hipStreamWaitEvent(s, ev_start, 0)) != hipSuccess) return (int)e;
+    int rc = a.wt_ready ? 0 : sv_transpose_cast_bf16(a.w_hh[l], H, 4 * H, H, w.whhT, 4L * H, s);
+    if (rc) return rc;
+    if (!a.wt_ready && l > 0 && (rc = sv_transpose_cast_bf16(a.w_ih[l], Fl, 4 * H, Fl, w.wihT, bf16_wiht_ld(H), s)))
+      return rc;
+    if (Bp != B && (e = sv_memset0(a.dgT[l], (size_t)4 * H * TBp * sizeof(bf16_t), s)) != hipSuccess)
+      return (int)e;
+    for (int c = nch - 1; c >= 0; --c) {
+      const int t0 = c * a.chunk, t1 = std::min(T, t0 + a.chunk);
+      if (l < L - 1 && (e = hipStreamWaitEvent(s, ev[(l + 1) * nch + c], 0)) != hipSuccess) return (int)e;
+      for (int t = t1 - 1; t >= t0; --t) {
+        const float* up = (l == L - 1) ? (t == T - 1 ? a.dh_last : nullptr) : a.dx[l + 1] + t * BH;
+        float* dcf_out = (t & 1) ? ws.dcf1 : ws.dcf0;
+        const float* dcf_in = (t == T - 1) ? nullptr : ((t & 1) ? ws.dcf0 : ws.dcf1);
+        launch_bwd_bf16(grid, s, t == T - 1 ? nullptr : dg[l] + (t + 1) * BG, w.whhT, up, dcf_in, a.gates[l] + t * BG,
+                        a.c_tm[l] + t * BH, t ? a.c_tm[l] + (t - 1) * BH : nullptr, dg[l] + t * BG, dcf_out, a.dgT[l],
+                        (long)TBp, t, Bp, B, H);
+        SV_LAUNCH_CHECK();
+      }
+      if (l > 0) {
+        rc = sv_gemm_bf16((t1 - t0) * B, Fl, 4 * H, dg[l] + t0 * BG, 4L * H, w.wihT, bf16_wiht_ld(H),
+                          a.dx[l] + (long)t0 * B * Fl, Fl, nullptr, nullptr, 0.f, ws.gws, s);
+        if (rc) return rc;
+      }
+      if ((e = hipEventRecord(ev[l * nch + c], s)) != hipSuccess) return (int)e;
+    }
+    rc = sv_gemm_bf16(4 * H, H, TBp, a.dgT[l], TBp, a.hT[l], a.ldhT, a.dw_hh[l], H, nullptr, nullptr, 0.f, ws.gws, s);
+    if (rc) return rc;
+    rc = sv_gemm_bf16(4 * H, Fl, TBp, a.dgT[l], TBp, a.xT[l], a.ld_xT[l], a.dw_ih[l], Fl, nullptr, nullptr, 0.f, ws.gws,
+                      s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(rowsum_bf16_kernel, dim3(4 * H), dim3(256), 0, s, a.dgT[l], (long)TBp, TBp, a.db_ih[l],
+                       a.db_hh ? a.db_hh[l] : nullptr);
+    SV_LAUNCH_CHECK();
+    if ((e = hipEventRecord(ev[L * nch + l], s)) != hipSuccess) return (int)e;
+  }
+  for (int l = 0; l < L; ++l)
+    if ((e = hipStreamWaitEvent(a.main, ev[L * nch + l], 0)) != hipSuccess) return (int)e;
+  return SV_OK;
+}
+}  // namespace
+
+// validates, fills BBwdArgs and dispatches to the schedule that `schedule` and the device select
 extern "C" int sv_lstm_stack_bwd_bf16(int L, int T, int B, int F, int H, const bf16_t* const* xT, const long* ld_xT,
                                       const float* const* w_ih, const float* const* w_hh, const bf16_t* const* gates,
                                       const float* const* c_tm, const bf16_t* const* hT, const float* dh_last,
                                       bf16_t* const* dg, bf16_t* const* dgT, float* const* dx, float* const* dw_ih,
                                       float* const* dw_hh, float* const* db_ih, float* const* db_hh, void* workspace,
-                                      int chunk, hipStream_t main, const hipStream_t* side, hipEvent_t* ev,
+                                      void* wt, int chunk, hipStream_t main, const hipStream_t* side, hipEvent_t* ev,
                                       void* sync_block, hipEvent_t* probe, int schedule) {
   if (L <= 0 || !xT || !ld_xT || !w_ih || !w_hh || !gates || !c_tm || !hT || !dh_last || !dg || !dgT || !dx ||
-      !dw_ih || !dw_hh || !db_ih || !workspace || !side || !ev || chunk <= 0)
+      !dw_ih || !dw_hh || !db_ih || !workspace || !wt || ((uintptr_t)wt & 255) || !side || !ev || chunk <= 0)
     return SV_EARG;
   if (schedule & ~SV_SCHED_MASK) return SV_EARG;
-  unsigned* sync = reinterpret_cast<unsigned*>(sync_block);
   if (T <= 0 || B <= 0 || F <= 0 || H <= 0 || F % 8 || H % 8) return SV_ESHAPE;
-  const int nch = (T + chunk - 1) / chunk;
-  const long BH = (long)B * H, BG = 4L * B * H;
-  const int Bp = (B + 7) & ~7;
-  const int TBp = T * Bp;
-  const long ldhT = (long)(T + 1) * Bp;
-  const size_t per = carve_bbwd(nullptr, T, B, std::max(F, H), H).total;
-  hipError_t e;
-  // the per-layer completion events (a caller's gradient buckets wait on them) of the persistent and
-  // wavefront schedules; SV_SCHED_NO_EVENTS: nobody waits, record none (each record idles the GPU)
-  const bool evs = !(schedule & SV_SCHED_NO_EVENTS);
-  // SV_SCHED_WT_READY: sv_lstm_weights_bf16 already wrote the transposes into this workspace
-  const bool wt_ready = schedule & SV_SCHED_WT_READY;
-  // SV_SCHED_CNT_READY: the stack forward zeroed the backward's counter channels and no backward
-  // has used this sync block since (the caller tracks that): no zeroing launches here
-  const bool cnt_ready = schedule & SV_SCHED_CNT_READY;
-  // every layer's whole-K weight-gradient tiles in one launch where they fit one round of the CUs
-  // (gemm_bf16_8qf_kernel; layer 0's N = F dW_ih after it on the narrow kernel), the split form
-  // (first pieces on the CUs the tiles leave free, their flags on channel SV_BWD_CH0 + WB_L) where
-  // at least 8 CUs are left over and the partials fit the GEMM scratch
-  auto plan_fullk = [&](G8Full& f, int& fP) -> bool {
-    const int cus = sv_stream_cus(main);
-    f = G8Full{};
-    fP = 0;
-    if (!(L == WB_L && gemm256_ok(4 * H, H, TBp) && TBp % 8 == 0 && ldhT % 8 == 0)) return false;
-    bool fullk = true;
-    f.K = TBp;
-    for (int l = 0; l < L; ++l) {
-      // upper layers: dW_ih beside dW_hh (input width H, 3 column tiles); layer 0 too (x0 tile):
-      // its F <= 256 columns as one partial column tile (x^T rows clamped, F columns stored) --
-      // the narrow GEMM after the launch re-read all of dG^T_0 for them (c5 rank 76 + 10 us)
-      const bool x0 = l == 0 && F <= G256_BM && F % 4 == 0;
-      const bool dual = l > 0 || x0;
-      G8FLayer& fl = f.lay[l];
-      fl.A = dgT[l];
-      fl.lda = TBp;
-      fl.B = hT[l];
-      fl.ldb = ldhT;
-      fl.B2 = dual ? xT[l] : nullptr;
-      fl.ldb2 = dual ? ld_xT[l] : 0;
-      fl.C1 = dw_hh[l];
-      fl.ldc1 = H;
-      fl.C2 = dual ? dw_ih[l] : nullptr;
-      fl.ldc2 = l > 0 ? H : F;
-      fl.n1 = H;
-      fl.N = l > 0 ? 2 * H : x0 ? H + G256_BM : H;
-      fl.f2 = x0 ? F : 0;
-      fl.tiles = (4 * H / G256_BM) * (fl.N / G256_BM);
-      fP += fl.tiles;
-      if (((uintptr_t)dgT[l] | (uintptr_t)hT[l] | (uintptr_t)dw_hh[l]) & 15) fullk = false;
-      if (dual && ((((uintptr_t)xT[l] | (uintptr_t)dw_ih[l]) & 15) || ld_xT[l] % 8 || fl.ldc2 % 4)) fullk = false;
-    }
-    fullk = fullk && fP <= cus;
-    const BBwdWs wsp = carve_bbwd((char*)workspace + per * (L - 1), T, B, std::max(F, H), H);
-    const int KT = TBp / G256_BK;
-    f.nsw = fullk ? (cus - fP) / 8 * 8 : 0;
-    if (f.nsw > 0) {
-      const int per_wg = (fP + f.nsw - 1) / f.nsw;  // first pieces per workgroup
-      f.S = KT / (per_wg + 1) - 2;    // (their stores and prologues: a little less)
-    }
-    if (f.nsw <= 0 || f.S < 4 || (size_t)fP * G256_BM * G256_BM * 4 > wsp.gbytes) f.nsw = f.S = 0;
-    if (f.S > 0) {
-      f.part = wsp.gws;
-      f.flag = sync + SV_SYNC_CNT + (size_t)(SV_BWD_CH0 + WB_L) * SV_PCNT_ROWS * SV_PCNT_STRIDE;
-      f.status = sync;
-      f.limit = sv_persist_limit();
-    }
-    return fullk;
-  };
-  // the whole-K launch, then layer 0's dW_ih and the layers' completion events
-  auto run_fullk = [&](const G8Full& f, int fP) -> int {
-    hipLaunchKernelGGL(gemm_bf16_8qf_kernel, dim3(f.nsw + fP + dbfin_blocks(f.fin, 512)), dim3(512), G256_LDS, main, f);
-    SV_LAUNCH_CHECK();
-    for (int l = L - 1; l >= 1 && evs; --l)
-      if ((e = hipEventRecord(ev[L * nch + l], main)) != hipSuccess) return (int)e;
-    if (!f.lay[0].f2) {  // layer 0's dW_ih (F > 256) on its own
-      const BBwdWs ws = carve_bbwd((char*)workspace, T, B, std::max(F, H), H);
-      if (int rc = sv_gemm_bf16(4 * H, F, TBp, dgT[0], TBp, xT[0], ld_xT[0], dw_ih[0], F, nullptr, nullptr, 0.f, ws.gws,
-                                main))
-        return rc;
-    }
-    if (evs && (e = hipEventRecord(ev[L * nch], main)) != hipSuccess) return (int)e;
-    return SV_OK;
-  };
-  if (sched_wave(schedule, H) && sv_wave_bwd_fits(L, B, H, sv_stream_cus(main))) {
-    if (!sync) return SV_EARG;
-    // layer-wavefront schedule: every layer's recurrence and upstream gradient dx in one launch
-    // (sv_persist3.hip, no dx GEMMs; bias gradients summed in the kernel), then per layer the
-    // weight gradients on `main`
-    const bf16_t* whhT_l[WB_L];
-    const bf16_t* wihT_l[WB_L];
-    for (int l = 0; l < L; ++l) {
-      const BBwdWs ws = carve_bbwd((char*)workspace + per * l, T, B, std::max(F, H), H);
-      whhT_l[l] = ws.whhT;
-      wihT_l[l] = l > 0 ? ws.wihT : nullptr;
-    }
-    int rc = wt_ready ? 0 : wbf_transposes(L, F, H, w_ih, w_hh, whhT_l, wihT_l, main);
-    if (rc) return rc;
-    G8Full f;
-    int fP;
-    const bool fullk = plan_fullk(f, fP);
-    // with the whole-K launch after it, the bias finalize rides on that launch (G8Full::fin)
-    rc = sv_wave_bwd_bf16(L, T, B, H, whhT_l, wihT_l, gates, c_tm, dh_last, dx, dgT, (char*)workspace + per * L,
-                              sync, main, db_ih, db_hh, probe ? probe[0] : nullptr, probe ? probe[1] : nullptr,
-                              bf16_wiht_ld(H), f.S > 0 ? fP : 0, SV_BWD_CH0, cnt_ready, fullk ? &f.fin : nullptr);
-    if (rc) return rc;
-    if (fullk) return run_fullk(f, fP);
-    for (int l = L - 1; l >= 0; --l) {
-      const int Fl = l == 0 ? F : H;
-      const BBwdWs ws = carve_bbwd((char*)workspace + per * l, T, B, std::max(F, H), H);
-      if ((rc = sv_gemm_bf16_dual(4 * H, H, Fl, TBp, dgT[l], TBp, hT[l], ldhT, dw_hh[l], H, xT[l], ld_xT[l], dw_ih[l],
-                                  Fl, ws.gws, main)))
-        return rc;
-      // layer l's gradients are complete: its all-reduce bucket (grad_ready) overlaps the lower
-      // layers' weight-gradient GEMMs (the recurrences are all done)
-      if (evs && (e = hipEventRecord(ev[L * nch + l], main)) != hipSuccess) return (int)e;
-    }
-    return SV_OK;
-  }
-  if (sched_persist(schedule, H) && sv_persist_bwd_fits(B, H, sv_stream_cus(main))) {
-    if (!sync) return SV_EARG;
-    // persistent schedule on `main`: per layer (top first) the whole-T recurrence in one launch
-    // (sv_persist.hip; bias gradients summed in the kernel), the whole-T dx GEMM straight from its
-    // fragment-order hand-off, then the layer's weight gradients (measured: on a side stream
-    // beside the next layer's recurrence 16.8 vs 16.6 ms at c3 -- the GEMM workgroups contend
-    // with the co-resident recurrence)
-    {  // every layer's W_hh^T / W_ih^T (bf16) in one launch
-      std::vector<const bf16_t*> whhT_l(L), wihT_l(L);  // any L (wbf_transposes batches 8 at a time)
-      for (int l = 0; l < L; ++l) {
-        const BBwdWs ws = carve_bbwd((char*)workspace + per * l, T, B, std::max(F, H), H);
-        whhT_l[l] = ws.whhT;
-        wihT_l[l] = l > 0 ? ws.wihT : nullptr;
-      }
-      if (int rc = wt_ready ? 0 : wbf_transposes(L, F, H, w_ih, w_hh, whhT_l.data(), wihT_l.data(), main)) return rc;
-    }
-    // the weight gradients of every layer after the last recurrence, as the layer wavefront's one
-    // whole-K launch (plan_fullk), where it applies; else per layer, split-K, after its recurrence
-    G8Full f;
-    int fP;
-    const bool fullk = SV_PERSIST_FULLK && plan_fullk(f, fP);
-    if (fullk && f.S > 0 && !cnt_ready) {  // the first pieces' flags (else zeroed by the forward)
-      if (int rc = sv_zero_counters(f.flag, 1, 0, fP, main)) return rc;
-    }
-    for (int l = L - 1; l >= 0; --l) {
-      const int Fl = l == 0 ? F : H;
-      const BBwdWs ws = carve_bbwd((char*)workspace + per * l, T, B, std::max(F, H), H);
-      int rc = 0;
-      const float* up = l == L - 1 ? dh_last : dx[l + 1];
-      bf16_t* dgf = (bf16_t*)((char*)workspace + per * L);
-      const bool afr = l > 0 && gemm_afrag_ok(T, B, Fl, H);  // dx reads dgf: no row-major dG
-      // layer l on channel SV_BWD_CH0 + l, pre-zeroed by the forward (cnt_ready) where the layers fit
-      // the channels, else each launch zeroing its own
-      const bool own = L <= SV_SYNC_CHANNELS - SV_BWD_CH0;
-      // the bias-gradient finalize rides on the next launch (the dx GEMM; layer 0's: the whole-K
-      // weight-gradient launch), before the next recurrence reuses the partials' slots in dgf
-      DbFin fin{};
-      if ((rc = sv_persist_bwd_bf16(T, B, H, ws.whhT, gates[l], c_tm[l], up, l < L - 1,
-                                    (afr || l == 0) ? nullptr : dg[l],  // layer 0 has no dx GEMM
-                                    dgT[l], dgf, main, sync, db_ih[l], db_hh ? db_hh[l] : nullptr,
-                                    probe ? probe[2 * l] : nullptr, probe ? probe[2 * l + 1] : nullptr,
-                                    SV_BWD_CH0 + (own ? l : 0), own && cnt_ready, &fin)))
-        return rc;
-      // the completion events of layers >= 1 (grad_ready: a caller's bucketed all-reduce) fire once
-      // the last recurrence is done, so collectives never share the device with a persistent launch
-      // (whose grid must be co-resident; a concurrent RCCL kernel would hold CUs it waits for) but
-      // overlap layer 0's weight-gradient GEMMs
-      for (int k = 1; l == 0 && k < L && evs && !fullk; ++k)
-        if ((e = hipEventRecord(ev[L * nch + k], main)) != hipSuccess) return (int)e;
-      if (afr) {
-        if ((rc = gemm_bf16_afrag(T, B, H, Fl, dgf, sv_persist_bm(B, H, sv_stream_cus(main)), ws.wihT, bf16_wiht_ld(H), dx[l],
-                                  Fl, ws.gws, main, fin)))
-          return rc;
-      } else if (l == 0 && fullk) {
-        f.fin = fin;
-      } else {
-        if ((rc = sv_dbfin_launch(fin, main))) return rc;
-        if (l > 0 && (rc = sv_gemm_bf16(T * B, Fl, 4 * H, dg[l], 4L * H, ws.wihT, bf16_wiht_ld(H), dx[l], Fl, nullptr,
-                                        nullptr, 0.f, ws.gws, main)))
-          return rc;
-      }
-      if (fullk) continue;
-      // dW_hh and dW_ih in one pass over dG^T (falls back to two GEMMs for layer 0's F = 40)
-      rc = sv_gemm_bf16_dual(4 * H, H, Fl, TBp, dgT[l], TBp, hT[l], ldhT, dw_hh[l], H, xT[l], ld_xT[l], dw_ih[l], Fl,
-                             ws.gws, main);
-      if (rc) return rc;
-    }
-    if (fullk) return run_fullk(f, fP);
-    if (evs && (e = hipEventRecord(ev[L * nch], main)) != hipSuccess) return (int)e;
-    return SV_OK;
-  }
-  // per-step schedule, layer-pipelined (sv_lstm_stack_bwd, sv_lstm.hip): each layer on side[l]
-  hipEvent_t ev_start = ev[L * nch + L];
-  if ((e = hipEventRecord(ev_start, main)) != hipSuccess) return (int)e;
-  const dim3 grid((H + BF_U - 1) / BF_U, (B + BF_BM - 1) / BF_BM);
-  for (int l = L - 1; l >= 0; --l) {
-    hipStream_t s = side[l];
-    const int Fl = l == 0 ? F : H;
-    const BBwdWs ws = carve_bbwd((char*)workspace + per * l, T, B, std::max(F, H), H);
-    if ((e = hipStreamWaitEvent(s, ev_start, 0)) != hipSuccess) return (int)e;
-    int rc = wt_ready ? 0 : sv_transpose_cast_bf16(w_hh[l], H, 4 * H, H, ws.whhT, 4L * H, s);
-    if (rc) return rc;
-    if (!wt_ready && l > 0 && (rc = sv_transpose_cast_bf16(w_ih[l], Fl, 4 * H, Fl, ws.wihT, bf16_wiht_ld(H), s)))
-      return rc;
-    if (Bp != B && (e = sv_memset0(dgT[l], (size_t)4 * H * TBp * sizeof(bf16_t), s)) != hipSuccess)
-      return (int)e;
-    for (int c = nch - 1; c >= 0; --c) {
-      const int t0 = c * chunk, t1 = std::min(T, t0 + chunk);
-      if (l < L - 1 && (e = hipStreamWaitEvent(s, ev[(l + 1) * nch + c], 0)) != hipSuccess) return (int)e;
-      for (int t = t1 - 1; t >= t0; --t) {
-        const float* up = (l == L - 1) ? (t == T - 1 ? dh_last : nullptr) : dx[l + 1] + t * BH;
-        float* dcf_out = (t & 1) ? ws.dcf1 : ws.dcf0;
-        const float* dcf_in = (t == T - 1) ? nullptr : ((t & 1) ? ws.dcf0 : ws.dcf1);
-        launch_bwd_bf16(grid, s, t == T - 1 ? nullptr : dg[l] + (t + 1) * BG, ws.whhT, up, dcf_in, gates[l] + t * BG,
-                        c_tm[l] + t * BH, t ? c_tm[l] + (t - 1) * BH : nullptr, dg[l] + t * BG, dcf_out, dgT[l],
-                        (long)TBp, t, Bp, B, H);
-        SV_LAUNCH_CHECK();
-      }
-      if (l > 0) {
-        rc = sv_gemm_bf16((t1 - t0) * B, Fl, 4 * H, dg[l] + t0 * BG, 4L * H, ws.wihT, bf16_wiht_ld(H),
-                          dx[l] + (long)t0 * B * Fl, Fl, nullptr, nullptr, 0.f, ws.gws, s);
-        if (rc) return rc;
-      }
-      if ((e = hipEventRecord(ev[l * nch + c], s)) != hipSuccess) return (int)e;
-    }
-    rc = sv_gemm_bf16(4 * H, H, TBp, dgT[l], TBp, hT[l], ldhT, dw_hh[l], H, nullptr, nullptr, 0.f, ws.gws, s);
-    if (rc) return rc;
-    rc = sv_gemm_bf16(4 * H, Fl, TBp, dgT[l], TBp, xT[l], ld_xT[l], dw_ih[l], Fl, nullptr, nullptr, 0.f, ws.gws, s);
-    if (rc) return rc;
-    hipLaunchKernelGGL(rowsum_bf16_kernel, dim3(4 * H), dim3(256), 0, s, dgT[l], (long)TBp, TBp, db_ih[l],
-                       db_hh ? db_hh[l] : nullptr);
-    SV_LAUNCH_CHECK();
-    if ((e = hipEventRecord(ev[L * nch + l], s)) != hipSuccess) return (int)e;
-  }
-  for (int l = 0; l < L; ++l)
-    if ((e = hipStreamWaitEvent(main, ev[L * nch + l], 0)) != hipSuccess) return (int)e;
-  return SV_OK;
+  BBwdArgs a{L, T, B, F, H, xT, ld_xT, w_ih, w_hh, gates, c_tm, hT, dh_last, dg, dgT, dx, dw_ih, dw_hh, db_ih, db_hh,
+             static_cast<char*>(workspace), wt, chunk, main, side, ev, reinterpret_cast<unsigned*>(sync_block), probe};
+  a.nch = (T + chunk - 1) / chunk;
+  a.BH = (long)B * H;
+  a.BG = 4L * B * H;
+  a.Bp = (B + 7) & ~7;
+  a.TBp = T * a.Bp;
+  a.ldhT = (long)(T + 1) * a.Bp;
+  a.per = carve_bbwd(nullptr, T, B, std::max(F, H), H).total;
+  a.evs = !(schedule & SV_SCHED_NO_EVENTS);
+  a.wt_ready = schedule & SV_SCHED_WT_READY;
+  a.cnt_ready = schedule & SV_SCHED_CNT_READY;
+  if (sched_wave(schedule, H) && sv_wave_bwd_fits(L, B, H, sv_stream_cus(main))) return a.sync ? bwd_wave(a) : SV_EARG;
+  if (sched_persist(schedule, H) && sv_persist_bwd_fits(B, H, sv_stream_cus(main)))
+    return a.sync ? bwd_persist(a) : SV_EARG;
+  return bwd_per_step(a);
 }

@@ -45,9 +45,7 @@ def _forward(x, params, precision, schedule, save, status):
     if precision not in _PRECISIONS:
         raise ValueError(f"precision must be one of {_PRECISIONS}, got {precision!r}")
     layers, w_p, b_p = _layers(params)
-    if precision == "bf16":
-        return ops.embedder_forward_bf16(x.contiguous(), layers, w_p, b_p, save=save, status=status, schedule=schedule)
-    return ops.embedder_forward(x.contiguous(), layers, w_p, b_p, save=save, status=status, schedule=schedule)
+    return ops.embedder_fwd(precision, x.contiguous(), layers, w_p, b_p, save=save, status=status, schedule=schedule)
 
 
 @torch.library.custom_op("sv::speech_embedder", mutates_args=(), device_types="cuda")
@@ -72,12 +70,8 @@ def speech_embedder_backward(x: Tensor, params: List[Tensor], demb: Tensor, prec
     _, st = _forward(x.float(), params, precision, schedule, True, status)
     layers, w_p, _ = _layers(params)
     grads, flat = ops._flat_grads(params, demb.device)
-    if precision == "bf16":
-        out = ops.embedder_backward_bf16(st, demb.contiguous(), layers, w_p, grads=grads, status=status,
-                                         schedule=schedule, need_dx=need_dx)
-    else:
-        out = ops.embedder_backward(st, demb.contiguous(), layers, w_p, grads=grads, need_dx=need_dx,
-                                    status=status, schedule=schedule)
+    out = ops.embedder_bwd(precision, st, demb.contiguous(), layers, w_p, grads=grads, need_dx=need_dx, status=status,
+                           schedule=schedule)
     call("sv_status_poison", status.ptr(), ptr(flat), flat.numel(), stream_of(flat))  # NaN on a timeout
     status.arm()
     ops._UNCHECKED.append(status)

@@ -5,6 +5,8 @@ plumbing; every FLOP of the path runs in the HIP kernels of libsv_ge2e.so.
 
   embedder_forward / embedder_backward   SpeechEmbedder.forward (speech_embedder_net.py:27-33)
                                          and its backward: 3-layer LSTM + Linear + L2 norm
+  embedder_forward_bf16 / _backward_bf16 the same with bf16 GEMM operands
+  embedder_fwd / embedder_bwd            either pair, chosen by a `precision` argument
   ge2e_forward / ge2e_backward           GE2ELoss.forward (speech_embedder_net.py:43-49)
   EmbedderFunction, GE2EFunction         autograd.Function glue (loss.backward() works)
   clip_sgd_step_                         clip_grad_norm_ + SGD.step (train_speech_embedder.py:63-65)
@@ -114,7 +116,8 @@ def _ws(nbytes, device):
 
 # ----------------------------------------------------------------------------- LSTM stack
 class EmbedderState:
-    """Activations saved by the forward for the backward (all time-major, fp32)."""
+    """Activations saved by the forward for the backward (all time-major; fp32, under bf16 the GEMM
+    operands x_tm / gates / hT / xT0 in bf16)."""
 
     def __init__(self):
         self.x_tm = []      # per layer input [T,B,F_l]
@@ -126,7 +129,105 @@ class EmbedderState:
         self.y = self.emb = self.ynorm = self.h_last = None
         self.T = self.B = self.H = self.P = 0
         self.bf16 = False
-        self.bws = None     # bf16: the stacked backward's workspace, its weight transposes already in
+        self.wt = None      # bf16, L > 1: the stack backward's weight transposes (sv_lstm_wt_bf16_size bytes)
+
+
+def _f32(shape, dev):
+    return torch.empty(shape, dtype=torch.float32, device=dev)
+
+
+def _bf(shape, dev):
+    return torch.empty(shape, dtype=torch.bfloat16, device=dev)
+
+
+def _proj_norm_fwd(st, h_last, w_p, b_p, s):
+    """Projection + L2 norm of h_last [B,H] (sv_proj_norm_fwd), saved into st; returns emb [B,P]."""
+    B, H, P, dev = st.B, st.H, st.P, h_last.device
+    y, emb, ynorm = _f32((B, P), dev), _f32((B, P), dev), _f32((B,), dev)
+    ws = _ws(lib().sv_proj_norm_workspace(B, H, P), dev)
+    call("sv_proj_norm_fwd", ptr(h_last), B, H, P, ptr(w_p), ptr(b_p), ptr(y), ptr(emb), ptr(ynorm), ptr(ws), s)
+    st.y, st.emb, st.ynorm, st.h_last = y, emb, ynorm, h_last
+    return emb
+
+
+def _proj_norm_bwd(st, demb, layers, w_p, grads, s):
+    """Backward of _proj_norm_fwd into the projection's two of ``grads`` (allocated here if None, in
+    parameter order [w_ih, w_hh, b_ih, b_hh]*L + [w_p, b_p]); returns (grads, dh_last [B,H])."""
+    B, H, P, L, dev = st.B, st.H, st.P, len(layers), demb.device
+    if grads is None:
+        grads = [torch.empty_like(t) for l in layers for t in l] + [torch.empty_like(w_p), _f32((P,), dev)]
+    dh_last = _f32((B, H), dev)
+    ws = _ws(lib().sv_proj_norm_workspace(B, H, P), dev)
+    call("sv_proj_norm_bwd", ptr(demb), ptr(st.emb), ptr(st.ynorm), ptr(st.h_last), B, H, P, ptr(w_p),
+         ptr(grads[4 * L]), ptr(grads[4 * L + 1]), ptr(dh_last), ptr(ws), s)
+    return grads, dh_last
+
+
+def _side(dev, role, L, nev):
+    """The (device, role) pool's L side streams and first nev events as host arrays, and its events."""
+    streams, events = _StreamPool.get(dev, role, L, nev)
+    sp = (ctypes.c_void_p * L)(*[st_.cuda_stream for st_ in streams])
+    ep = (ctypes.c_void_p * nev)(*[e.cuda_event for e in events[:nev]])
+    return sp, ep, events
+
+
+def _stack_fwd(dtype, x_tm, w_ih, w_hh, layers, gs, cs, hs, hbs, hTs, prod, sched, status, probe, s):
+    """sv_lstm_fwd of L > 1 layers: x_tm, w_ih, w_hh, gs, hTs (and hbs, bf16 only) in ``dtype``."""
+    T, B, F = x_tm.shape
+    L, H, dev = len(layers), cs[0].shape[2], x_tm.device
+    nch = (T + PIPELINE_CHUNK - 1) // PIPELINE_CHUNK
+    sp, ep, _ = _side(dev, "fwd", L, L * nch + 1)
+    sync, own = _own_status(status, dev)
+    call("sv_lstm_fwd", dtype, L, T, B, F, H, ptr(x_tm), _parr(w_ih), _parr(w_hh), _parr([l[2] for l in layers]),
+         _parr([l[3] for l in layers]), _parr(gs), _parr(cs), _parr(hs), _parr(hbs) if hbs else None, _parr(hTs),
+         PIPELINE_CHUNK, s, sp, ep, prod, sched, sync.ptr(), _evarr(probe))
+    if dtype == SV_DTYPE_BF16:  # (the bf16 stack forward zeroes the backward's channels, every schedule)
+        sync.bwd_counters_clean = True
+    _release_status(sync, own)
+
+
+def _stack_bwd(dtype, st, layers, grads, dh_last, dgs, dgTs, ws, wt, prod, sched, status, probe, kstamp, grad_ready,
+               late_head, s):
+    """sv_lstm_bwd of L > 1 layers (no input gradient): dgs / dgTs [4H, T*Bp] in ``dtype``, ws its
+    scratch, wt the bf16 weight transposes (None for fp32).  Then the layers' grad_ready calls, each
+    behind the event the library recorded for it; late_head: the projection's too."""
+    T, B, H, L, dev = st.T, st.B, st.H, len(layers), dh_last.device
+    F0 = st.x_tm[0].shape[2]
+    Bp, esz = dgTs[0].shape[1] // T, dgTs[0].element_size()
+    dxs = [None] + [_f32((T, B, H), dev) for _ in range(L - 1)]
+    # layer l's input transposed: x^T, then the layer below's h^T from column block 1 (= h_0 .. h_{T-1})
+    xT = [ptr(st.xT0)] + [ptr(st.hT[l - 1]) + Bp * esz for l in range(1, L)]
+    ld = [T * Bp] + [(T + 1) * Bp] * (L - 1)
+    nch = (T + PIPELINE_CHUNK - 1) // PIPELINE_CHUNK
+    sp, ep, events = _side(dev, "bwd", L, L * nch + L + 1)
+    sync, own = _own_status(status, dev)
+    if dtype == SV_DTYPE_BF16:
+        if sync.bwd_counters_clean:  # the forward zeroed the backward's counters, none used since
+            sched |= SV_SCHED_CNT_READY
+        sync.bwd_counters_clean = False
+    call("sv_lstm_bwd", dtype, L, T, B, F0, H, (ctypes.c_void_p * L)(*xT), (ctypes.c_long * L)(*ld),
+         _parr([l[0] for l in layers]), _parr([l[1] for l in layers]), _parr(st.gates), _parr(st.c_tm),
+         _parr(st.hT), ptr(dh_last), _parr(dgs), _parr(dgTs), _parr(dxs),
+         _parr([grads[4 * l] for l in range(L)]), _parr([grads[4 * l + 1] for l in range(L)]),
+         _parr([grads[4 * l + 2] for l in range(L)]), _parr([grads[4 * l + 3] for l in range(L)]), ptr(ws), ptr(wt),
+         PIPELINE_CHUNK, s, sp, ep, prod, _evarr(probe), ptr(kstamp), sched, sync.ptr())
+    _release_status(sync, own)
+    if grad_ready:
+        if late_head:
+            # behind the event the library records right after the last recurrence (the status word
+            # is final there, and with the persistent recurrences a collective must not run beside
+            # them), not behind all of main: the buckets then overlap layer 0's dx / dW GEMMs
+            grad_ready(L, events[L * nch + L - 1])
+        for l in range(L - 1, -1, -1):
+            grad_ready(l, events[L * nch + l])
+
+
+def _dx_batch_first(dx, s):
+    """dx [T,B,F] time-major -> [B,T,F]."""
+    T, B, F = dx.shape
+    dxb = _f32((B, T, F), dx.device)
+    call("sv_frames_to_time_major", ptr(dx), ptr(dxb), T, B, F, s)
+    return dxb
 
 
 def embedder_forward(x, layers, w_p, b_p, save=True, products="mfma_f32", status=None, probe=None, schedule="auto"):
@@ -141,71 +242,39 @@ def embedder_forward(x, layers, w_p, b_p, save=True, products="mfma_f32", status
     require_device(x, w_p, b_p, *[t for l in layers for t in l])
     B, T, F = x.shape
     H = layers[0][1].shape[1]
-    P = w_p.shape[0]
+    L = len(layers)
     dev = x.device
     s = stream_of(x)
+    if prod and L == 1:
+        raise ValueError("the bf16x6 product mode runs on the layer-pipelined stack only (L > 1)")
     st = EmbedderState()
-    st.T, st.B, st.H, st.P = T, B, H, P
-    x_tm = torch.empty((T, B, F), dtype=torch.float32, device=dev)
+    st.T, st.B, st.H, st.P = T, B, H, w_p.shape[0]
+    x_tm = _f32((T, B, F), dev)
     call("sv_frames_to_time_major", ptr(x), ptr(x_tm), B, T, F, s)
     Bp = (B + 3) // 4 * 4
     if save:  # layer-0 input transposed, [F, T*Bp] (column block t = x_t^T, padding columns zero)
         if Bp == B:
-            st.xT0 = torch.empty((F, T * B), dtype=torch.float32, device=dev)
+            st.xT0 = _f32((F, T * B), dev)
             call("sv_transpose", ptr(x_tm), F, T * B, F, ptr(st.xT0), T * B, s)
         else:
             st.xT0 = torch.zeros((F, T * Bp), dtype=torch.float32, device=dev)
             for t in range(T):
                 call("sv_transpose", ptr(x_tm[t]), F, B, F, ptr(st.xT0) + 4 * t * Bp, T * Bp, s)
-    inp = x_tm
-    L = len(layers)
-    if PIPELINE_CHUNK > 0 and L > 1:
-        gs = [torch.empty((T, B, 4 * H), dtype=torch.float32, device=dev) for _ in range(L)]
-        cs = [torch.empty((T, B, H), dtype=torch.float32, device=dev) for _ in range(L)]
-        hs = [torch.empty((T + 1, B, H), dtype=torch.float32, device=dev) for _ in range(L)]
-        hTs = [torch.empty((H, (T + 1) * Bp), dtype=torch.float32, device=dev) if save else None for _ in range(L)]
-        nch = (T + PIPELINE_CHUNK - 1) // PIPELINE_CHUNK
-        streams, events = _StreamPool.get(dev, "fwd", L, L * nch + 1)
-        sp = (ctypes.c_void_p * L)(*[st_.cuda_stream for st_ in streams])
-        ep = (ctypes.c_void_p * (L * nch + 1))(*[e.cuda_event for e in events[:L * nch + 1]])
-        ps, own = _own_status(status, dev)
-        call("sv_lstm_fwd", SV_DTYPE_F32, L, T, B, F, H, ptr(x_tm), _parr([l[0] for l in layers]),
-             _parr([l[1] for l in layers]), _parr([l[2] for l in layers]), _parr([l[3] for l in layers]),
-             _parr(gs), _parr(cs), _parr(hs), None, _parr(hTs), PIPELINE_CHUNK, s, sp, ep, prod, sched, ps.ptr(),
-             _evarr(probe))
-        _release_status(ps, own)
-        if save:
-            st.x_tm = [x_tm] + [h[1:] for h in hs[:-1]]
-            st.gates, st.c_tm, st.h_tm, st.hT = gs, cs, hs, hTs
-        layers_done = True
-        inp = hs[-1][1:]
+    gs = [_f32((T, B, 4 * H), dev) for _ in range(L)]
+    cs = [_f32((T, B, H), dev) for _ in range(L)]
+    hs = [_f32((T + 1, B, H), dev) for _ in range(L)]
+    hTs = [_f32((H, (T + 1) * Bp), dev) if save else None for _ in range(L)]
+    if L > 1:
+        _stack_fwd(SV_DTYPE_F32, x_tm, [l[0] for l in layers], [l[1] for l in layers], layers, gs, cs, hs, None, hTs,
+                   prod, sched, status, probe, s)
     else:
-        layers_done = False
-    if not layers_done and prod:
-        raise ValueError("the bf16x6 product mode runs on the layer-pipelined stack only (SV_PIPELINE_CHUNK > 0, L > 1)")
-    for (w_ih, w_hh, b_ih, b_hh) in ([] if layers_done else layers):
-        Fl = inp.shape[2]
-        gates = torch.empty((T, B, 4 * H), dtype=torch.float32, device=dev)
-        c_tm = torch.empty((T, B, H), dtype=torch.float32, device=dev)
-        h_tm = torch.empty((T + 1, B, H), dtype=torch.float32, device=dev)
-        hT = torch.empty((H, (T + 1) * Bp), dtype=torch.float32, device=dev) if save else None
-        call("sv_lstm_layer_fwd", ptr(inp), T, B, Fl, H, ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh), ptr(gates),
-             ptr(c_tm), ptr(h_tm), ptr(hT), s)
-        if save:
-            st.x_tm.append(inp)
-            st.gates.append(gates)
-            st.c_tm.append(c_tm)
-            st.h_tm.append(h_tm)
-            st.hT.append(hT)
-        inp = h_tm[1:]
-    h_last = inp[T - 1]
-    y = torch.empty((B, P), dtype=torch.float32, device=dev)
-    emb = torch.empty((B, P), dtype=torch.float32, device=dev)
-    ynorm = torch.empty((B,), dtype=torch.float32, device=dev)
-    ws = _ws(lib().sv_proj_norm_workspace(B, H, P), dev)
-    call("sv_proj_norm_fwd", ptr(h_last), B, H, P, ptr(w_p), ptr(b_p), ptr(y), ptr(emb), ptr(ynorm), ptr(ws), s)
-    st.y, st.emb, st.ynorm, st.h_last = y, emb, ynorm, h_last
-    return emb, st
+        w_ih, w_hh, b_ih, b_hh = layers[0]
+        call("sv_lstm_layer_fwd", ptr(x_tm), T, B, F, H, ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh), ptr(gs[0]),
+             ptr(cs[0]), ptr(hs[0]), ptr(hTs[0]), s)
+    if save:
+        st.x_tm = [x_tm] + [h[1:] for h in hs[:-1]]
+        st.gates, st.c_tm, st.h_tm, st.hT = gs, cs, hs, hTs
+    return _proj_norm_fwd(st, hs[-1][T], w_p, b_p, s), st
 
 
 def embedder_backward(st, demb, layers, w_p, grads=None, need_dx=False, grad_ready=None, products="mfma_f32",
@@ -231,20 +300,12 @@ def embedder_backward(st, demb, layers, w_p, grads=None, need_dx=False, grad_rea
     sched = schedule_flags(schedule) | (0 if grad_ready else SV_SCHED_NO_EVENTS)
     demb = demb.contiguous()
     require_device(demb)
-    T, B, H, P = st.T, st.B, st.H, st.P
+    T, B, H = st.T, st.B, st.H
     dev = demb.device
     s = stream_of(demb)
     L = len(layers)
-    if grads is None:
-        grads = []
-        for (w_ih, w_hh, b_ih, b_hh) in layers:
-            grads += [torch.empty_like(w_ih), torch.empty_like(w_hh), torch.empty_like(b_ih), torch.empty_like(b_hh)]
-        grads += [torch.empty_like(w_p), torch.empty((P,), dtype=torch.float32, device=dev)]
-    dh_last = torch.empty((B, H), dtype=torch.float32, device=dev)
-    ws = _ws(lib().sv_proj_norm_workspace(B, H, P), dev)
-    call("sv_proj_norm_bwd", ptr(demb), ptr(st.emb), ptr(st.ynorm), ptr(st.h_last), B, H, P, ptr(w_p),
-         ptr(grads[4 * L]), ptr(grads[4 * L + 1]), ptr(dh_last), ptr(ws), s)
-    stacked = PIPELINE_CHUNK > 0 and L > 1 and not need_dx
+    grads, dh_last = _proj_norm_bwd(st, demb, layers, w_p, grads, s)
+    stacked = L > 1 and not need_dx
     # under the persistent schedule the projection bucket is enqueued behind the stack backward
     # (a collective must not run beside a persistent launch); else it overlaps the BPTT
     with torch.cuda.device(dev):  # (the library answers for the current device)
@@ -253,49 +314,23 @@ def embedder_backward(st, demb, layers, w_p, grads=None, need_dx=False, grad_rea
         grad_ready(L, None)
     if prod and not stacked:
         raise ValueError("the bf16x6 product mode runs on the layer-pipelined stack only")
-    Fmax = max(st.x_tm[l].shape[2] for l in range(L))
     Bp = (B + 3) // 4 * 4
     if stacked:
-        F0 = st.x_tm[0].shape[2]
-        ws = _ws(lib().sv_lstm_bwd_workspace(SV_DTYPE_F32, L, T, B, F0, H), dev)
-        dgs = [torch.empty((T, B, 4 * H), dtype=torch.float32, device=dev) for _ in range(L)]
-        dgTs = [torch.empty((4 * H, T * Bp), dtype=torch.float32, device=dev) for _ in range(L)]
-        dxs = [None] + [torch.empty((T, B, H), dtype=torch.float32, device=dev) for _ in range(L - 1)]
-        xT = [ptr(st.xT0)] + [ptr(st.hT[l - 1]) + Bp * 4 for l in range(1, L)]
-        ld = [T * Bp] + [(T + 1) * Bp] * (L - 1)
-        nch = (T + PIPELINE_CHUNK - 1) // PIPELINE_CHUNK
-        nev = L * nch + L + 1
-        streams, events = _StreamPool.get(dev, "bwd", L, nev)
-        ps, own = _own_status(status, dev)
-        sp = (ctypes.c_void_p * L)(*[st_.cuda_stream for st_ in streams])
-        ep = (ctypes.c_void_p * nev)(*[e.cuda_event for e in events[:nev]])
-        call("sv_lstm_bwd", SV_DTYPE_F32, L, T, B, F0, H, (ctypes.c_void_p * L)(*xT), (ctypes.c_long * L)(*ld),
-             _parr([l[0] for l in layers]), _parr([l[1] for l in layers]), _parr(st.gates), _parr(st.c_tm),
-             _parr(st.hT), ptr(dh_last), _parr(dgs), _parr(dgTs), _parr(dxs),
-             _parr([grads[4 * l] for l in range(L)]), _parr([grads[4 * l + 1] for l in range(L)]),
-             _parr([grads[4 * l + 2] for l in range(L)]), _parr([grads[4 * l + 3] for l in range(L)]), ptr(ws),
-             PIPELINE_CHUNK, s, sp, ep, prod, _evarr(probe), ptr(kstamp) if kstamp is not None else None, sched,
-             ps.ptr())
-        _release_status(ps, own)
-        if grad_ready:
-            if late_head:
-                # behind the event the library records right after the last recurrence (the status
-                # word is final there), not behind all of main: the buckets then overlap layer 0's
-                # dx / dW GEMMs
-                grad_ready(L, events[L * nch + L - 1] if L > 1 else None)
-            for l in range(L - 1, -1, -1):
-                grad_ready(l, events[L * nch + l])
+        ws = _ws(lib().sv_lstm_bwd_workspace(SV_DTYPE_F32, L, T, B, st.x_tm[0].shape[2], H), dev)
+        dgs = [_f32((T, B, 4 * H), dev) for _ in range(L)]
+        dgTs = [_f32((4 * H, T * Bp), dev) for _ in range(L)]
+        _stack_bwd(SV_DTYPE_F32, st, layers, grads, dh_last, dgs, dgTs, ws, None, prod, sched, status, probe, kstamp,
+                   grad_ready, late_head, s)
         return grads
+    Fmax = max(st.x_tm[l].shape[2] for l in range(L))
     ws = _ws(lib().sv_lstm_layer_bwd_workspace(T, B, Fmax, H), dev)
-    dgates = torch.empty((T, B, 4 * H), dtype=torch.float32, device=dev)
-    dgT = torch.empty((4 * H, T * Bp), dtype=torch.float32, device=dev)
+    dgates = _f32((T, B, 4 * H), dev)
+    dgT = _f32((4 * H, T * Bp), dev)
     dh_up, full = dh_last, 0
-    dx_out = None
     for l in range(L - 1, -1, -1):
         w_ih, w_hh, _, _ = layers[l]
         Fl = st.x_tm[l].shape[2]
-        want_dx = l > 0 or need_dx
-        dx = torch.empty((T, B, Fl), dtype=torch.float32, device=dev) if want_dx else None
+        dx = _f32((T, B, Fl), dev) if (l > 0 or need_dx) else None
         if l == 0:
             xT, ld_xT = ptr(st.xT0), T * Bp
         else:  # previous layer's h^T, column blocks 1..T (= h_0 .. h_{T-1})
@@ -306,20 +341,10 @@ def embedder_backward(st, demb, layers, w_p, grads=None, need_dx=False, grad_rea
         if grad_ready:
             grad_ready(l, None)
         dh_up, full = dx, 1
-        if l == 0:
-            dx_out = dx
-    if need_dx:
-        dxb = torch.empty((B, T, dx_out.shape[2]), dtype=torch.float32, device=dev)
-        call("sv_frames_to_time_major", ptr(dx_out), ptr(dxb), T, B, dx_out.shape[2], s)  # [T,B,F] -> [B,T,F]
-        return grads, dxb
-    return grads
+    return (grads, _dx_batch_first(dh_up, s)) if need_dx else grads
 
 
 # ----------------------------------------------------------------------------- bf16 operands
-def _bf(shape, dev):
-    return torch.empty(shape, dtype=torch.bfloat16, device=dev)
-
-
 def embedder_forward_bf16(x, layers, w_p, b_p, save=True, status=None, probe=None, schedule="auto"):
     """Mixed-precision forward (BASELINE config c3): bf16 GEMM operands, fp32 accumulation,
     bf16 storage of the x-projection and of the activated gates saved for the backward, fp32
@@ -332,79 +357,53 @@ def embedder_forward_bf16(x, layers, w_p, b_p, save=True, status=None, probe=Non
     require_device(x, w_p, b_p, *[t for l in layers for t in l])
     B, T, F = x.shape
     H = layers[0][1].shape[1]
-    P = w_p.shape[0]
     dev = x.device
     s = stream_of(x)
     Bp = (B + 7) // 8 * 8
     st = EmbedderState()
-    st.T, st.B, st.H, st.P, st.bf16 = T, B, H, P, True
+    st.T, st.B, st.H, st.P, st.bf16 = T, B, H, w_p.shape[0], True
     x_bf = _bf((T, B, F), dev)
     L = len(layers)
-    fused_x = F <= 64
+    fused_x = F <= 64  # x -> time-major bf16 and x^T: in the weights' launch below (sv_lstm_prep_bf16)
     if save:  # layer 0's dW_ih operand x^T [F][T Bp] (padding columns zero)
         st.xT0 = (torch.empty if fused_x or Bp == B else torch.zeros)((F, T * Bp), dtype=torch.bfloat16, device=dev)
-    if fused_x:  # x -> time-major bf16 and x^T: in the weights' launch below (sv_lstm_prep_bf16)
-        srcs, dsts = [], []
-    else:
-        x_tm = torch.empty((T, B, F), dtype=torch.float32, device=dev)
+    if not fused_x:
+        x_tm = _f32((T, B, F), dev)
         call("sv_frames_to_time_major", ptr(x), ptr(x_tm), B, T, F, s)
-        srcs, dsts = [x_tm], [x_bf]
         if save:
             if Bp == B:
                 call("sv_transpose_cast_bf16", ptr(x_tm), F, T * B, F, ptr(st.xT0), T * B, s)
             else:
                 for t in range(T):
                     call("sv_transpose_cast_bf16", ptr(x_tm[t]), F, B, F, ptr(st.xT0) + 2 * t * Bp, T * Bp, s)
-    if srcs:  # the time-major frames' cast (F > 64)
-        call("sv_cast_bf16", ptr(srcs[0]), ptr(dsts[0]), srcs[0].numel(), s)
+        call("sv_cast_bf16", ptr(x_tm), ptr(x_bf), x_tm.numel(), s)
     # every layer's bf16 weights in one launch (sv_lstm_weights_bf16); when the stacked backward
-    # follows, also its weight transposes, into the backward workspace it will be handed
+    # follows, also its weight transposes, into the buffer st.wt it will be handed
     # (SV_SCHED_WT_READY: the backward launches no transposes)
     wbf = [(_bf(w_ih.shape, dev), _bf(w_hh.shape, dev)) for (w_ih, w_hh, _, _) in layers]
-    if save and PIPELINE_CHUNK > 0 and L > 1:
-        st.bws = _ws(lib().sv_lstm_bwd_workspace(SV_DTYPE_BF16, L, T, B, F, H), dev)
+    if save and L > 1:
+        st.wt = _ws(lib().sv_lstm_wt_bf16_size(L, F, H), dev)
     wargs = (_parr([l[0] for l in layers]), _parr([l[1] for l in layers]), _parr([w[0] for w in wbf]),
-             _parr([w[1] for w in wbf]), ptr(st.bws) if st.bws is not None else None, s)
-    if fused_x:  # the frames' part in the same launch (sv_lstm_prep_bf16)
-        call("sv_lstm_prep_bf16", L, T, B, F, H, ptr(x), ptr(x_bf), ptr(st.xT0) if save else None, Bp, *wargs)
+             _parr([w[1] for w in wbf]), ptr(st.wt), s)
+    if fused_x:  # the frames' part in the same launch
+        call("sv_lstm_prep_bf16", L, T, B, F, H, ptr(x), ptr(x_bf), ptr(st.xT0), Bp, *wargs)
     else:
-        call("sv_lstm_weights_bf16", L, T, B, F, H, *wargs)
-    inp = x_bf
+        call("sv_lstm_weights_bf16", L, F, H, *wargs)
     gs = [_bf((T, B, 4 * H), dev) for _ in range(L)]  # bf16 x-projection in, bf16 activations out
-    cs = [torch.empty((T, B, H), dtype=torch.float32, device=dev) for _ in range(L)]
-    hs = [torch.empty((T + 1, B, H), dtype=torch.float32, device=dev) for _ in range(L)]
+    cs = [_f32((T, B, H), dev) for _ in range(L)]
+    hs = [_f32((T + 1, B, H), dev) for _ in range(L)]
     hbs = [_bf((T + 1, B, H), dev) for _ in range(L)]
     hTs = [_bf((H, (T + 1) * Bp), dev) if save else None for _ in range(L)]
-    if PIPELINE_CHUNK > 0 and L > 1:
-        nch = (T + PIPELINE_CHUNK - 1) // PIPELINE_CHUNK
-        streams, events = _StreamPool.get(dev, "fwd", L, L * nch + 1)
-        sp = (ctypes.c_void_p * L)(*[st_.cuda_stream for st_ in streams])
-        ep = (ctypes.c_void_p * (L * nch + 1))(*[e.cuda_event for e in events[:L * nch + 1]])
-        sync, own = _own_status(status, dev)
-        call("sv_lstm_fwd", SV_DTYPE_BF16, L, T, B, F, H, ptr(x_bf), _parr([w[0] for w in wbf]),
-             _parr([w[1] for w in wbf]), _parr([l[2] for l in layers]), _parr([l[3] for l in layers]),
-             _parr(gs), _parr(cs), _parr(hs), _parr(hbs), _parr(hTs), PIPELINE_CHUNK, s, sp, ep, 0, sched,
-             sync.ptr(), _evarr(probe))
-        sync.bwd_counters_clean = True  # (the stack forward zeroes the backward's channels, every schedule)
-        _release_status(sync, own)
+    if L > 1:
+        _stack_fwd(SV_DTYPE_BF16, x_bf, [w[0] for w in wbf], [w[1] for w in wbf], layers, gs, cs, hs, hbs, hTs, 0,
+                   sched, status, probe, s)
     else:
-        for l, (w_ih, w_hh, b_ih, b_hh) in enumerate(layers):
-            Fl = inp.shape[2]
-            call("sv_lstm_layer_fwd_bf16", ptr(inp), T, B, Fl, H, ptr(wbf[l][0]), ptr(wbf[l][1]), ptr(b_ih),
-                 ptr(b_hh), ptr(gs[l]), ptr(cs[l]), ptr(hs[l]), ptr(hbs[l]), ptr(hTs[l]), s)
-            inp = hbs[l][1:]
+        call("sv_lstm_layer_fwd_bf16", ptr(x_bf), T, B, F, H, ptr(wbf[0][0]), ptr(wbf[0][1]), ptr(layers[0][2]),
+             ptr(layers[0][3]), ptr(gs[0]), ptr(cs[0]), ptr(hs[0]), ptr(hbs[0]), ptr(hTs[0]), s)
     if save:
         st.x_tm = [x_bf] + [h[1:] for h in hbs[:-1]]
         st.gates, st.c_tm, st.h_tm, st.hT = gs, cs, hs, hTs
-    h_tm = hs[-1]
-    h_last = st.h_tm[-1][T] if save else h_tm[T]
-    y = torch.empty((B, P), dtype=torch.float32, device=dev)
-    emb = torch.empty((B, P), dtype=torch.float32, device=dev)
-    ynorm = torch.empty((B,), dtype=torch.float32, device=dev)
-    ws = _ws(lib().sv_proj_norm_workspace(B, H, P), dev)
-    call("sv_proj_norm_fwd", ptr(h_last), B, H, P, ptr(w_p), ptr(b_p), ptr(y), ptr(emb), ptr(ynorm), ptr(ws), s)
-    st.y, st.emb, st.ynorm, st.h_last = y, emb, ynorm, h_last
-    return emb, st
+    return _proj_norm_fwd(st, hs[-1][T], w_p, b_p, s), st
 
 
 def embedder_forward_dvec_bf16(x, layers, w_p, b_p):
@@ -438,59 +437,30 @@ def embedder_backward_bf16(st, demb, layers, w_p, grads=None, grad_ready=None, s
     sched = schedule_flags(schedule) | (0 if grad_ready else SV_SCHED_NO_EVENTS)  # (as embedder_backward)
     demb = demb.contiguous()
     require_device(demb)
-    T, B, H, P = st.T, st.B, st.H, st.P
+    T, B, H = st.T, st.B, st.H
     dev = demb.device
     s = stream_of(demb)
     L = len(layers)
     Bp = (B + 7) // 8 * 8
-    if grads is None:
-        grads = []
-        for (w_ih, w_hh, b_ih, b_hh) in layers:
-            grads += [torch.empty_like(w_ih), torch.empty_like(w_hh), torch.empty_like(b_ih), torch.empty_like(b_hh)]
-        grads += [torch.empty_like(w_p), torch.empty((P,), dtype=torch.float32, device=dev)]
-    dh_last = torch.empty((B, H), dtype=torch.float32, device=dev)
-    ws = _ws(lib().sv_proj_norm_workspace(B, H, P), dev)
-    call("sv_proj_norm_bwd", ptr(demb), ptr(st.emb), ptr(st.ynorm), ptr(st.h_last), B, H, P, ptr(w_p),
-         ptr(grads[4 * L]), ptr(grads[4 * L + 1]), ptr(dh_last), ptr(ws), s)
-    Fmax = max(st.x_tm[l].shape[2] for l in range(L))
-    if PIPELINE_CHUNK > 0 and L > 1 and not need_dx:
+    grads, dh_last = _proj_norm_bwd(st, demb, layers, w_p, grads, s)
+    if L > 1 and not need_dx:
         F0 = st.x_tm[0].shape[2]
-        if st.bws is not None:  # the forward wrote the weight transposes into it (sv_lstm_weights_bf16)
-            ws, sched = st.bws, sched | SV_SCHED_WT_READY
-        else:
-            ws = _ws(lib().sv_lstm_bwd_workspace(SV_DTYPE_BF16, L, T, B, F0, H), dev)
+        ws = _ws(lib().sv_lstm_bwd_workspace(SV_DTYPE_BF16, L, T, B, F0, H), dev)
+        wt = st.wt
+        if wt is not None:  # the forward wrote the weight transposes into it (sv_lstm_weights_bf16)
+            sched |= SV_SCHED_WT_READY
+        else:               # the backward transposes into it itself
+            wt = _ws(lib().sv_lstm_wt_bf16_size(L, F0, H), dev)
         dgs = [_bf((T, B, 4 * H), dev) for _ in range(L)]
         dgTs = [_bf((4 * H, T * Bp), dev) for _ in range(L)]
-        dxs = [None] + [torch.empty((T, B, H), dtype=torch.float32, device=dev) for _ in range(L - 1)]
-        xT = [ptr(st.xT0)] + [ptr(st.hT[l - 1]) + Bp * 2 for l in range(1, L)]
-        ld = [T * Bp] + [(T + 1) * Bp] * (L - 1)
-        nch = (T + PIPELINE_CHUNK - 1) // PIPELINE_CHUNK
-        nev = L * nch + L + 1
-        streams, events = _StreamPool.get(dev, "bwd", L, nev)
-        sp = (ctypes.c_void_p * L)(*[st_.cuda_stream for st_ in streams])
-        ep = (ctypes.c_void_p * nev)(*[e.cuda_event for e in events[:nev]])
-        sync, own = _own_status(status, dev)
-        if sync.bwd_counters_clean:  # the forward zeroed the backward's counters, none used since
-            sched |= SV_SCHED_CNT_READY
-        sync.bwd_counters_clean = False
-        call("sv_lstm_bwd", SV_DTYPE_BF16, L, T, B, F0, H, (ctypes.c_void_p * L)(*xT), (ctypes.c_long * L)(*ld),
-             _parr([l[0] for l in layers]), _parr([l[1] for l in layers]), _parr(st.gates), _parr(st.c_tm),
-             _parr(st.hT), ptr(dh_last), _parr(dgs), _parr(dgTs), _parr(dxs),
-             _parr([grads[4 * l] for l in range(L)]), _parr([grads[4 * l + 1] for l in range(L)]),
-             _parr([grads[4 * l + 2] for l in range(L)]), _parr([grads[4 * l + 3] for l in range(L)]), ptr(ws),
-             PIPELINE_CHUNK, s, sp, ep, 0, _evarr(probe), None, sched, sync.ptr())
-        _release_status(sync, own)
+        # the projection bucket too is enqueued behind the stack backward (late_head), for every schedule
+        _stack_bwd(SV_DTYPE_BF16, st, layers, grads, dh_last, dgs, dgTs, ws, wt, 0, sched, status, probe, None,
+                   grad_ready, True, s)
         st.dgT = dgTs  # the weight-gradient GEMMs' A operands (tests check dW against them)
-        if grad_ready:
-            # the projection bucket is enqueued behind the stack backward: with the persistent
-            # recurrences a collective must not run beside them (sv_lstm_stack_bwd_bf16): behind the
-            # event recorded once every recurrence (and layer L-1's gradients) is done
-            grad_ready(L, events[L * nch + L - 1] if L > 1 else None)
-            for l in range(L - 1, -1, -1):
-                grad_ready(l, events[L * nch + l])
         return grads
     if grad_ready:
         grad_ready(L, None)
+    Fmax = max(st.x_tm[l].shape[2] for l in range(L))
     ws = _ws(lib().sv_lstm_layer_bwd_bf16_workspace(T, B, Fmax, H), dev)
     dg = _bf((T, B, 4 * H), dev)
     dgT = _bf((4 * H, T * Bp), dev)
@@ -502,7 +472,7 @@ def embedder_backward_bf16(st, demb, layers, w_p, grads=None, grad_ready=None, s
         wihT = _bf((Fl, 4 * H), dev)
         call("sv_transpose_cast_bf16", ptr(w_ih), Fl, 4 * H, Fl, ptr(wihT), 4 * H, s)
         call("sv_transpose_cast_bf16", ptr(w_hh), H, 4 * H, H, ptr(whhT), 4 * H, s)
-        dx = torch.empty((T, B, Fl), dtype=torch.float32, device=dev) if (l > 0 or need_dx) else None
+        dx = _f32((T, B, Fl), dev) if (l > 0 or need_dx) else None
         if l == 0:
             xT, ld_xT = ptr(st.xT0), T * Bp
         else:
@@ -513,11 +483,22 @@ def embedder_backward_bf16(st, demb, layers, w_p, grads=None, grad_ready=None, s
         if grad_ready:
             grad_ready(l, None)
         dh_up, full = dx, 1
-    if need_dx:
-        dxb = torch.empty((B, T, dh_up.shape[2]), dtype=torch.float32, device=dev)
-        call("sv_frames_to_time_major", ptr(dh_up), ptr(dxb), T, B, dh_up.shape[2], s)  # [T,B,F] -> [B,T,F]
-        return grads, dxb
-    return grads
+    return (grads, _dx_batch_first(dh_up, s)) if need_dx else grads
+
+
+def embedder_fwd(precision, x, layers, w_p, b_p, products="mfma_f32", **kw):
+    """embedder_forward_bf16 (precision "bf16") or embedder_forward (any other; ``products`` is its)."""
+    if precision == "bf16":
+        return embedder_forward_bf16(x, layers, w_p, b_p, **kw)
+    return embedder_forward(x, layers, w_p, b_p, products=products, **kw)
+
+
+def embedder_bwd(precision, st, demb, layers, w_p, products="mfma_f32", kstamp=None, **kw):
+    """embedder_backward_bf16 (precision "bf16") or embedder_backward (any other; ``products`` and
+    ``kstamp`` are its)."""
+    if precision == "bf16":
+        return embedder_backward_bf16(st, demb, layers, w_p, **kw)
+    return embedder_backward(st, demb, layers, w_p, products=products, kstamp=kstamp, **kw)
 
 
 def _flat_grads(params, dev):
@@ -547,12 +528,8 @@ class EmbedderFunction(torch.autograd.Function):
         # a forward-only loop keeps _UNCHECKED bounded)
         check_persistent_status()
         ctx.status = PersistStatus(x.device)
-        if precision == "bf16":
-            emb, st = embedder_forward_bf16(x.contiguous(), layers, w_p, b_p, save=True, status=ctx.status,
-                                            schedule=schedule)
-        else:
-            emb, st = embedder_forward(x.contiguous(), layers, w_p, b_p, save=True, products=products,
-                                       status=ctx.status, schedule=schedule)
+        emb, st = embedder_fwd(precision, x.contiguous(), layers, w_p, b_p, products=products, save=True,
+                               status=ctx.status, schedule=schedule)
         # checked even if no backward follows (eval, d-vectors, anything under no_grad): a hand-off
         # timeout in this forward raises at the next call / check_persistent_status()
         ctx.status.arm()
@@ -570,12 +547,8 @@ class EmbedderFunction(torch.autograd.Function):
         layers = [tuple(params[4 * l:4 * l + 4]) for l in range(L)]
         need_dx = ctx.needs_input_grad[0]
         grads, flat = _flat_grads(params, demb.device)
-        if ctx.precision == "bf16":
-            out = embedder_backward_bf16(ctx.st, demb, layers, params[4 * L], grads=grads, status=ctx.status,
-                                         schedule=ctx.schedule, need_dx=need_dx)
-        else:
-            out = embedder_backward(ctx.st, demb, layers, params[4 * L], grads=grads, need_dx=need_dx,
-                                    products=ctx.products, status=ctx.status, schedule=ctx.schedule)
+        out = embedder_bwd(ctx.precision, ctx.st, demb, layers, params[4 * L], products=ctx.products, grads=grads,
+                           need_dx=need_dx, status=ctx.status, schedule=ctx.schedule)
         call("sv_status_poison", ctx.status.ptr(), ptr(flat), flat.numel(), stream_of(flat))
         ctx.status.arm()
         if ctx.status not in _UNCHECKED:

@@ -42,8 +42,7 @@ import torch
 import torch.distributed as dist
 
 from ._lib import PersistStatus, call, ptr, stream_of
-from .ops import (clip_sgd_step2_, embedder_backward, embedder_backward_bf16, embedder_forward,
-                  embedder_forward_bf16)
+from .ops import clip_sgd_step2_, embedder_bwd, embedder_fwd
 from .sharded_ge2e import ShardedGE2E
 
 
@@ -171,24 +170,22 @@ class GE2ETrainer:
         layers = net.LSTM_stack.layer_params()
         w_p, b_p = net.projection.weight, net.projection.bias
         w, b = self.loss_mod.w, self.loss_mod.b
-        bf16 = getattr(net, "precision", "f32") == "bf16"
+        precision = getattr(net, "precision", "f32")
+        bf16 = precision == "bf16"
         products = getattr(net, "f32_products", "mfma_f32")
         schedule = getattr(net, "schedule", "auto")
         chunks = (bf16_row_chunks(x.shape[0], layers[0][1].shape[1], schedule, len(layers), x.shape[1], x.shape[2])
                   if bf16 else [(0, x.shape[0])])
-        if bf16 and len(chunks) > 1:
+        if len(chunks) > 1:  # (bf16 only)
             xf = x.float()
-            outs = [embedder_forward_bf16(xf[r0:r1].contiguous(), layers, w_p, b_p, status=self.status,
-                                          probe=probe.get("fwd") if i == 0 else None, schedule=schedule)
+            outs = [embedder_fwd(precision, xf[r0:r1].contiguous(), layers, w_p, b_p, status=self.status,
+                                 probe=probe.get("fwd") if i == 0 else None, schedule=schedule)
                     for i, (r0, r1) in enumerate(chunks)]
             emb = torch.cat([o[0] for o in outs])
             st = [o[1] for o in outs]
-        elif bf16:
-            emb, st = embedder_forward_bf16(x.float().contiguous(), layers, w_p, b_p, status=self.status,
-                                            probe=probe.get("fwd"), schedule=schedule)
         else:
-            emb, st = embedder_forward(x.float().contiguous(), layers, w_p, b_p, products=products,
-                                       status=self.status, probe=probe.get("fwd"), schedule=schedule)
+            emb, st = embedder_fwd(precision, x.float().contiguous(), layers, w_p, b_p, products=products,
+                                   status=self.status, probe=probe.get("fwd"), schedule=schedule)
         E = emb.view(N, M, emb.shape[1])
         dp = self.dp
         # data parallel: the local loss partial goes to the head bucket's all-reduce (no collective)
@@ -218,7 +215,7 @@ class GE2ETrainer:
                         # last recurrence, so the word is final (the per-step schedules never set it)
                         call("sv_status_to_flag", self.status.ptr(), ptr(self.flags), stream_of(self.flags))
                     works.append(dist.all_reduce(self.flat_g[lo:hi], group=self.group, async_op=True))
-        if bf16 and len(chunks) > 1:
+        if len(chunks) > 1:
             # chunk 0 writes the gradient buffer, the others a scratch copy added into it; the
             # buckets go once the sum is complete
             dEf = dE.view(N * M, -1)
@@ -230,22 +227,18 @@ class GE2ETrainer:
                     self._gtmp_views.append(self._gtmp[off:off + g.numel()].view_as(g))
                     off += g.numel()
             for i, (r0, r1) in enumerate(chunks):
-                embedder_backward_bf16(st[i], dEf[r0:r1], layers, w_p,
-                                       grads=self.grad_views if i == 0 else self._gtmp_views,
-                                       status=self.status, probe=probe.get("bwd") if i == 0 else None,
-                                       schedule=schedule)
+                embedder_bwd(precision, st[i], dEf[r0:r1], layers, w_p,
+                             grads=self.grad_views if i == 0 else self._gtmp_views, status=self.status,
+                             probe=probe.get("bwd") if i == 0 else None, schedule=schedule)
                 if i > 0:
                     self.flat_g[:self.n].add_(self._gtmp[:self.n])
             if ready:
                 for k in range(len(self.buckets) - 1, -1, -1):
                     ready(k, None)
-        elif bf16:
-            embedder_backward_bf16(st, dE.view(N * M, -1), layers, w_p, grads=self.grad_views, grad_ready=ready,
-                                   status=self.status, probe=probe.get("bwd"), schedule=schedule)
         else:
-            embedder_backward(st, dE.view(N * M, -1), layers, w_p, grads=self.grad_views, grad_ready=ready,
-                              products=products, probe=probe.get("bwd"), kstamp=probe.get("kstamp"),
-                              status=self.status, schedule=schedule)
+            embedder_bwd(precision, st, dE.view(N * M, -1), layers, w_p, grads=self.grad_views, grad_ready=ready,
+                         products=products, probe=probe.get("bwd"), kstamp=probe.get("kstamp"),
+                         status=self.status, schedule=schedule)
         for wk in works:
             wk.wait()  # the current (main) stream waits for every bucket
         if dp:

@@ -296,10 +296,10 @@ def test_wavefront_weight_gradients_against_fp64_of_same_operands(N, M, T):
 @pytest.mark.gpu
 @pytest.mark.parametrize("B,T,schedule", [(80, 24, "auto"), (320, 12, "auto"), (64, 8, "per_step")])
 def test_weights_bf16_transposes_handed_to_the_backward(B, T, schedule):
-    """sv_lstm_weights_bf16 (ABI v10): the forward's one launch writes every layer's bf16 weights
-    and, into the stack backward's workspace, the transposes that backward would otherwise form;
+    """sv_lstm_weights_bf16: the forward's one launch writes every layer's bf16 weights and, into the
+    transpose buffer st.wt, the transposes the stack backward would otherwise form;
     SV_SCHED_WT_READY makes the backward use them.  The gradients must be bit-identical to a
-    backward that transposes on its own (st.bws dropped), under the wavefront (B = 80), persistent
+    backward that transposes on its own (st.wt dropped), under the wavefront (B = 80), persistent
     (B = 320) and per-step schedules; the row-major copies must equal torch's bf16 rounding."""
     import recipe
     import torch
@@ -325,23 +325,23 @@ def test_weights_bf16_transposes_handed_to_the_backward(B, T, schedule):
     out = []
     for handed in (True, False):
         emb, st = ops.embedder_forward_bf16(x, layers, wp, bp, save=True, schedule=schedule)
-        assert st.bws is not None
+        assert st.wt is not None
         if not handed:
-            st.bws = None
+            st.wt = None
         out.append([g.clone() for g in ops.embedder_backward_bf16(st, demb, layers, wp, schedule=schedule)])
     torch.cuda.synchronize()
     for a, b in zip(*out):
         assert torch.equal(a, b)
-    # the row-major copies alone (no workspace) against torch's RNE rounding
+    # the row-major copies alone (no transpose buffer) against torch's RNE rounding
     wih = [torch.empty_like(l[0], dtype=torch.bfloat16) for l in layers]
     whh = [torch.empty_like(l[1], dtype=torch.bfloat16) for l in layers]
-    call("sv_lstm_weights_bf16", 3, T, B, F, H, _parr([l[0] for l in layers]), _parr([l[1] for l in layers]),
+    call("sv_lstm_weights_bf16", 3, F, H, _parr([l[0] for l in layers]), _parr([l[1] for l in layers]),
          _parr(wih), _parr(whh), None, stream_of(x))
     torch.cuda.synchronize()
     for l in range(3):
         assert torch.equal(wih[l], layers[l][0].to(torch.bfloat16))
         assert torch.equal(whh[l], layers[l][1].to(torch.bfloat16))
-    # sv_lstm_prep_bf16 (ABI v11): the frames' launch folded into the weights' one -- the same bytes
+    # sv_lstm_prep_bf16: the frames' launch folded into the weights' one -- the same bytes
     # as sv_frames_to_bf16 + sv_lstm_weights_bf16 (padding columns of x^T included)
     Bp = (B + 7) // 8 * 8
     outs = []
@@ -356,12 +356,62 @@ def test_weights_bf16_transposes_handed_to_the_backward(B, T, schedule):
             call("sv_lstm_prep_bf16", 3, T, B, F, H, x.data_ptr(), xb.data_ptr(), xT.data_ptr(), Bp, *wargs)
         else:
             call("sv_frames_to_bf16", x.data_ptr(), B, T, F, xb.data_ptr(), xT.data_ptr(), Bp, stream_of(x))
-            call("sv_lstm_weights_bf16", 3, T, B, F, H, *wargs)
+            call("sv_lstm_weights_bf16", 3, F, H, *wargs)
         torch.cuda.synchronize()
         outs.append([xb, xT] + wi + wh)
     for a, b in zip(*outs):
         assert torch.equal(a.view(torch.int16), b.view(torch.int16))
     assert torch.equal(outs[0][0].float(), x.transpose(0, 1).bfloat16().float())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B,T", [(80, 24), (320, 12)])
+def test_bf16_forward_keeps_only_its_state_and_the_transposes(B, T):
+    """What embedder_forward_bf16(save=True) leaves allocated while emb and st are held: the tensors
+    the state documents -- x_bf, xT0, per layer gates, c_tm, h_tm, h_bf, hT, then y, emb, ynorm --
+    plus the weight-transpose buffer st.wt (sv_lstm_wt_bf16_size bytes, independent of T and B),
+    within 1 MiB of allocator rounding.  The stack backward's scratch (per layer T * ceil(B/32) * 128
+    * H * 2 bytes of fragment-order hand-off alone, ~14 MB at (80, 24)) is the backward's to
+    allocate, not the forward's to park on the state."""
+    import recipe
+    import torch
+    from conftest import model_dims
+    from pytorch_speaker_verification_amd import ops
+    from pytorch_speaker_verification_amd._lib import lib
+    from pytorch_speaker_verification_amd.speech_embedder_net import SpeechEmbedder
+    dev = torch.device("cuda", 0)
+    dims = (40, 768, 3, 256)
+    F, H, L, P = dims
+    sd = recipe.make_weights(91, *dims, scale=3.0)
+    with model_dims(*dims):
+        net = SpeechEmbedder()
+    with torch.no_grad():
+        for k, v in net.state_dict().items():
+            v.copy_(torch.as_tensor(sd[k]))
+    net = net.to(dev)
+    layers = net.LSTM_stack.layer_params()
+    wp, bp = net.projection.weight, net.projection.bias
+    x = torch.as_tensor(recipe.make_frames(700, B, T, F)).to(dev)
+    ops.check_persistent_status(wait=True)
+    torch.cuda.synchronize()
+    before = torch.cuda.memory_allocated(dev)
+    emb, st = ops.embedder_forward_bf16(x, layers, wp, bp, save=True)
+    torch.cuda.synchronize()
+    delta = torch.cuda.memory_allocated(dev) - before
+    Bp = (B + 7) // 8 * 8
+    per_layer = (2 * T * B * 4 * H            # gates (bf16)
+                 + 4 * T * B * H              # c_tm
+                 + 4 * (T + 1) * B * H        # h_tm
+                 + 2 * (T + 1) * B * H        # h_bf
+                 + 2 * H * (T + 1) * Bp)      # hT (bf16)
+    documented = (2 * T * B * F + 2 * F * T * Bp   # x_bf, xT0
+                  + L * per_layer
+                  + 4 * (2 * B * P + B))           # y, emb, ynorm
+    wt = lib().sv_lstm_wt_bf16_size(L, F, H)
+    print(f"\nMEASURED bf16_forward_held_bytes.B{B}.T{T} {delta} (documented {documented} + wt {wt})")
+    assert delta <= documented + wt + (1 << 20), (delta, documented, wt)
+    assert st.wt.numel() * 4 >= wt
+    assert emb.shape == (B, P)
 
 
 @pytest.mark.gpu
