@@ -12,6 +12,11 @@ Follows the reference:
 
 ``params`` is a dict keyed by the reference state_dict names (tests/golden/recipe.py).
 Pure numpy loops over time: use only at small sizes.
+
+The layer and embedder functions take ``dtype`` (default float64: the oracle).  With
+``dtype=np.float32`` every array and every accumulation is fp32 -- the oracle's fp32 twin, the
+yardstick of what fp32 arithmetic itself loses on the same inputs (tests/test_gpu_lstm_blocks.py
+scales its tolerances by it).
 """
 from __future__ import annotations
 
@@ -24,15 +29,16 @@ def _sig(x):
     return 1.0 / (1.0 + np.exp(-x))
 
 
-def lstm_layer_forward(x, Wih, Whh, bih, bhh):
+def lstm_layer_forward(x, Wih, Whh, bih, bhh, dtype=np.float64):
     """x [B,T,F] -> (h [B,T,H], cache).  One nn.LSTM layer."""
+    x, Wih, Whh, bih, bhh = (np.asarray(a, dtype) for a in (x, Wih, Whh, bih, bhh))
     B, T, _ = x.shape
     H = Whh.shape[1]
-    h = np.zeros((B, H))
-    c = np.zeros((B, H))
-    hs = np.zeros((B, T, H))
-    cs = np.zeros((B, T, H))
-    acts = np.zeros((B, T, 4 * H))
+    h = np.zeros((B, H), dtype)
+    c = np.zeros((B, H), dtype)
+    hs = np.zeros((B, T, H), dtype)
+    cs = np.zeros((B, T, H), dtype)
+    acts = np.zeros((B, T, 4 * H), dtype)
     for t in range(T):
         g = x[:, t] @ Wih.T + bih + h @ Whh.T + bhh
         i, f, gg, o = _sig(g[:, :H]), _sig(g[:, H:2 * H]), np.tanh(g[:, 2 * H:3 * H]), _sig(g[:, 3 * H:])
@@ -44,21 +50,24 @@ def lstm_layer_forward(x, Wih, Whh, bih, bhh):
     return hs, (x, hs, cs, acts)
 
 
-def lstm_layer_backward(dhs, Wih, Whh, cache):
-    """dhs [B,T,H] gradient w.r.t. the layer's outputs -> (dx, dWih, dWhh, db)."""
-    x, hs, cs, acts = cache
+def lstm_layer_backward(dhs, Wih, Whh, cache, dtype=np.float64, return_dg=False):
+    """dhs [B,T,H] gradient w.r.t. the layer's outputs -> (dx, dWih, dWhh, db); with return_dg also
+    the gradient w.r.t. the pre-activations, dG [B,T,4H] (gate order i, f, g, o)."""
+    dhs, Wih, Whh = (np.asarray(a, dtype) for a in (dhs, Wih, Whh))
+    x, hs, cs, acts = (np.asarray(a, dtype) for a in cache)
     B, T, H = hs.shape
     dWih = np.zeros_like(Wih)
     dWhh = np.zeros_like(Whh)
-    db = np.zeros(4 * H)
+    db = np.zeros(4 * H, dtype)
     dx = np.zeros_like(x)
-    dh_next = np.zeros((B, H))
-    dc_next = np.zeros((B, H))
+    dGs = np.zeros((B, T, 4 * H), dtype)
+    dh_next = np.zeros((B, H), dtype)
+    dc_next = np.zeros((B, H), dtype)
     for t in range(T - 1, -1, -1):
         i, f, g, o = (acts[:, t, k * H:(k + 1) * H] for k in range(4))
         c = cs[:, t]
-        c_prev = cs[:, t - 1] if t > 0 else np.zeros((B, H))
-        h_prev = hs[:, t - 1] if t > 0 else np.zeros((B, H))
+        c_prev = cs[:, t - 1] if t > 0 else np.zeros((B, H), dtype)
+        h_prev = hs[:, t - 1] if t > 0 else np.zeros((B, H), dtype)
         dh = dhs[:, t] + dh_next
         tc = np.tanh(c)
         dc = dc_next + dh * o * (1 - tc * tc)
@@ -67,52 +76,55 @@ def lstm_layer_backward(dhs, Wih, Whh, cache):
         dg = dc * i * (1 - g * g)
         do = dh * tc * o * (1 - o)
         dG = np.concatenate([di, df, dg, do], axis=1)
+        dGs[:, t] = dG
         dWih += dG.T @ x[:, t]
         dWhh += dG.T @ h_prev
         db += dG.sum(axis=0)
         dx[:, t] = dG @ Wih
         dh_next = dG @ Whh
         dc_next = dc * f
-    return dx, dWih, dWhh, db
+    return (dx, dWih, dWhh, db, dGs) if return_dg else (dx, dWih, dWhh, db)
 
 
-def embedder_forward(params, x, num_layer):
+def embedder_forward(params, x, num_layer, dtype=np.float64):
     """speech_embedder_net.py:27-33.  x [B,T,F] -> (emb [B,P], cache)."""
-    inp = np.asarray(x, np.float64)
+    inp = np.asarray(x, dtype)
     caches = []
     for l in range(num_layer):
-        p = lambda n: np.asarray(params[f"LSTM_stack.{n}_l{l}"], np.float64)  # noqa: E731
-        inp, cache = lstm_layer_forward(inp, p("weight_ih"), p("weight_hh"), p("bias_ih"), p("bias_hh"))
+        p = lambda n: np.asarray(params[f"LSTM_stack.{n}_l{l}"], dtype)  # noqa: E731
+        inp, cache = lstm_layer_forward(inp, p("weight_ih"), p("weight_hh"), p("bias_ih"), p("bias_hh"), dtype)
         caches.append(cache)
     last = inp[:, -1]
-    Wp = np.asarray(params["projection.weight"], np.float64)
-    bp = np.asarray(params["projection.bias"], np.float64)
+    Wp = np.asarray(params["projection.weight"], dtype)
+    bp = np.asarray(params["projection.bias"], dtype)
     y = last @ Wp.T + bp
     n = np.linalg.norm(y, axis=1, keepdims=True)
     emb = y / n
     return emb, (caches, last, y, n)
 
 
-def embedder_backward(params, demb, cache, num_layer):
-    """Gradients of every parameter (dict keyed like params) given d emb."""
+def embedder_backward(params, demb, cache, num_layer, dtype=np.float64, return_dx=False):
+    """Gradients of every parameter (dict keyed like params) given d emb; with return_dx also the
+    gradient w.r.t. the input frames: (grads, dx [B,T,F])."""
     caches, last, y, n = cache
+    demb = np.asarray(demb, dtype)
     emb = y / n
-    Wp = np.asarray(params["projection.weight"], np.float64)
+    Wp = np.asarray(params["projection.weight"], dtype)
     dy = (demb - emb * (demb * emb).sum(axis=1, keepdims=True)) / n
     grads = {"projection.weight": dy.T @ last, "projection.bias": dy.sum(axis=0)}
     B, T, H = caches[-1][1].shape
-    dhs = np.zeros((B, T, H))
+    dhs = np.zeros((B, T, H), dtype)
     dhs[:, -1] = dy @ Wp
     for l in range(num_layer - 1, -1, -1):
-        Wih = np.asarray(params[f"LSTM_stack.weight_ih_l{l}"], np.float64)
-        Whh = np.asarray(params[f"LSTM_stack.weight_hh_l{l}"], np.float64)
-        dx, dWih, dWhh, db = lstm_layer_backward(dhs, Wih, Whh, caches[l])
+        Wih = np.asarray(params[f"LSTM_stack.weight_ih_l{l}"], dtype)
+        Whh = np.asarray(params[f"LSTM_stack.weight_hh_l{l}"], dtype)
+        dx, dWih, dWhh, db = lstm_layer_backward(dhs, Wih, Whh, caches[l], dtype)
         grads[f"LSTM_stack.weight_ih_l{l}"] = dWih
         grads[f"LSTM_stack.weight_hh_l{l}"] = dWhh
         grads[f"LSTM_stack.bias_ih_l{l}"] = db
         grads[f"LSTM_stack.bias_hh_l{l}"] = db.copy()
         dhs = dx
-    return grads
+    return (grads, dhs) if return_dx else grads
 
 
 def clip_coef(grads, max_norm):
