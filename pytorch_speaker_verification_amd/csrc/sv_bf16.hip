@@ -479,7 +479,7 @@ BPlan plan_bf16(int M, int N, int K) {
   const long tiles = (long)((M + p.bm - 1) / p.bm) * ((N + p.bn - 1) / p.bn);
   const long slots = small ? 1024 : 512;
   int sk = 1;
-  if (tiles < slots) {  // the wave-quantised split-K model of plan_gemm (sv_lstm.hip), at ~600 TF/s
+  if (tiles < slots) {  // the wave-quantised split-K model of plan_gemm (sv_gemm_f32.hip), at ~600 TF/s
     const double rate = 600e12 / (double)slots, hbm = 5e12;
     const int kmax = std::max(1, std::min(32, K / 1024));
     double best = 1e30;
@@ -693,7 +693,7 @@ int sv_gemm_bf16_dual(int M, int N1, int N2, int K, const bf16_t* A, long lda, c
 
 // ---- narrow bf16 NT GEMM (N <= 48): layer 0's dW_ih = dG^T x (M = 4H, N = F = 40, K = T B) ----
 // The 64 x 64 tiles padded N = 40 to 64 and streamed dG^T (629 MB at c3) at 4.6 TB/s (138 us).  The
-// fp32 narrow kernel's layout (sv_lstm.hip) in bf16: a workgroup is 128 rows x 48 columns over a K
+// fp32 narrow kernel's layout (sv_gemm_f32.hip) in bf16: a workgroup is 128 rows x 48 columns over a K
 // chunk, v_mfma_f32_16x16x32_bf16 (B first: a lane's 4 accumulators are 4 consecutive C columns),
 // each wave 32 rows (2 x 3 blocks); LDS images [rows][64 k] (128 B) with 16-B chunk c of row r at
 // c ^ (r & 7), filled by LDS-DMA, two stages; split-K slabs reduced by slab_reduce_bf_kernel.

@@ -17,6 +17,7 @@ typedef short bf16x8 __attribute__((ext_vector_type(8)));
 #define SV_EALIGN -2
 #define SV_ESHAPE -3
 
+// ---- the fp32 GEMM's translation unit (sv_gemm_f32.hip) ----
 // fp32 GEMM of the C ABI's sv_gemm_f32 (include/sv_ge2e.h) under the calling thread's current
 // product mode; F32ProductScope sets that mode for one entry point's duration
 // fine: split K in chunks down to 128 when the tiles leave most of the chip idle (the projection's
@@ -24,7 +25,7 @@ typedef short bf16x8 __attribute__((ext_vector_type(8)));
 int gemm_f32(int a_kcontig, int b_kcontig, int M, int N, int K, const float* A, long lda, const float* B, long ldb,
              float* C, long ldc, const float* bias0, const float* bias1, float beta, float* workspace,
              hipStream_t stream, bool fine = false);
-// the projection forward with the row norm fused into the split-K reduce (sv_lstm.hip); returns 0
+// the projection forward with the row norm fused into the split-K reduce; returns 0
 // where that form does not apply (the caller then runs gemm_f32 and its own norm)
 int proj_norm_fused(const float* h, int B, int K, int P, const float* W, const float* bias, float* y, float* emb,
                     float* ynorm, float* workspace, hipStream_t stream, int* rc);
@@ -33,6 +34,17 @@ struct F32ProductScope {
   explicit F32ProductScope(int mode);
   ~F32ProductScope();
 };
+// the K2 / K3 step kernels' variant under the current product mode: 0 exact, 1 x6, 2 x3
+int k2_x();
+int k3_x();
+// dx = dG W_ih of the fp32 persistent backward with A read from its fragment-order hand-off dgf:
+// dx_afrag_bn gives the column tile (256 / 128) where that form applies under the current product
+// mode, else -1 (the caller then runs gemm_f32 on the row-major dG); skws: gf_sk_bytes() of
+// stream-K scratch (NULL: no stream-K form)
+int dx_afrag_bn(int T, int B, int H, int Fl);
+size_t gf_sk_bytes();
+int gemm_f32_dx_afrag(int bn, const float* dgf, int T, int B, int H, const float* wihT, long ldw, int Fl, float* dx,
+                      hipStream_t s, void* skws = nullptr);
 
 // fp32 W-stationary persistent recurrences of one layer (sv_persist_f32.hip): H = 768, 64-row x
 // 32-unit tiles co-resident on `cus` CUs; dgf: sv_persist_f32_bwd_scratch bytes (16-B aligned)

@@ -12,6 +12,9 @@
 #include "sv_common.h"
 
 #define SV_BK 16
+// k-tile depth of the k-major main loops' users: the fp32 GEMM (sv_gemm_f32.hip) and the K2 / K3
+// step kernels (sv_lstm.hip)
+#define SV_BKM 32
 
 // ---------------------------------------------------------------------------
 // row maps: tile-local row r -> global row (k-contig) or column (r-contig) index,

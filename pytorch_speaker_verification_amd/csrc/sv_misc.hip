@@ -195,6 +195,57 @@ __global__ __launch_bounds__(256) void proj_bwd_tiles_kernel(const float* __rest
   __syncthreads();
   if (w == 0 && c < P) db[c] = lds[lane] + lds[64 + lane] + lds[128 + lane] + lds[192 + lane];
 }
+// ---- column sums (sv_colsum of the C ABI) ----
+// column sums of X[R, C] (row-major): partial[chunk][C] over row chunks
+__global__ void colsum_partial_kernel(const float* __restrict__ X, int R, int C, int rows_per_chunk,
+                                      float* __restrict__ partial) {
+  const int col = blockIdx.x * blockDim.x + threadIdx.x;
+  const int chunk = blockIdx.y;
+  if (col >= C) return;
+  const int r0 = chunk * rows_per_chunk, r1 = min(R, r0 + rows_per_chunk);
+  float s = 0.f;
+#pragma unroll 8
+  for (int r = r0; r < r1; ++r) s += X[(long)r * C + col];
+  partial[(long)chunk * C + col] = s;
+}
+__global__ void colsum_final_kernel(const float* __restrict__ partial, int nchunk, int C, float* __restrict__ out0,
+                                    float* __restrict__ out1) {
+  const int col = blockIdx.x * blockDim.x + threadIdx.x;
+  if (col >= C) return;
+  float s = 0.f;
+  for (int k = 0; k < nchunk; ++k) s += partial[(long)k * C + col];
+  out0[col] = s;
+  if (out1) out1[col] = s;
+}
+
+// rows per partial-sum chunk: about 1024 workgroups in all, chunks of 32..1024 rows, so a small R
+// (the projection's B rows) still spreads over many workgroups instead of one thread walking
+// every row, and a large R keeps the final pass short
+static int colsum_rows(int R, int C) {
+  const int target = std::max(1, 1024 / ((C + 255) / 256));
+  int rpc = (R + target - 1) / target;
+  rpc = (rpc + 31) / 32 * 32;
+  return std::min(1024, std::max(32, rpc));
+}
+
+extern "C" size_t sv_colsum_workspace(int R, int C) {
+  const int rpc = colsum_rows(R, C);
+  return (size_t)((R + rpc - 1) / rpc) * C * sizeof(float);
+}
+
+extern "C" int sv_colsum(const float* X, int R, int C, float* out, float* workspace, hipStream_t stream) {
+  if (!X || !out || !workspace || R <= 0 || C <= 0) return SV_EARG;
+  const int rows_per_chunk = colsum_rows(R, C);
+  const int nchunk = (R + rows_per_chunk - 1) / rows_per_chunk;
+  hipLaunchKernelGGL(colsum_partial_kernel, dim3((C + 255) / 256, nchunk), dim3(256), 0, stream, X, R, C,
+                     rows_per_chunk, workspace);
+  SV_LAUNCH_CHECK();
+  hipLaunchKernelGGL(colsum_final_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, workspace, nchunk, C, out,
+                     nullptr);
+  SV_LAUNCH_CHECK();
+  return SV_OK;
+}
+
 static bool proj_tiles_ok(int B, int H, int P, const void* h, const void* W, const void* dy) {
   return H % 4 == 0 && P % 4 == 0 && !(((uintptr_t)h | (uintptr_t)W | (uintptr_t)dy) & 15);
 }
@@ -226,10 +277,14 @@ extern "C" int sv_proj_norm_bwd(const float* demb, const float* emb, const float
                                 float* workspace, hipStream_t stream) {
   if (!demb || !emb || !ynorm || !h_last || !w_p || !dw_p || !db_p || !dh_last || !workspace) return SV_EARG;
   float* dy = workspace;
-  float* gws = workspace + ((size_t)B * P * sizeof(float) + 255) / 256 * 64;
+  // the MFMA-tile kernel where its operands are aligned, else the small kernel where it fits.  No
+  // third form: what fits neither (H % 4, a misaligned h_last / w_p, or P % 4 / a misaligned dy
+  // with B > 128 or P > 256) the fp32 GEMM's alignment checks reject as well
+  const bool tiles = proj_tiles_ok(B, H, P, h_last, w_p, dy);
+  if (!tiles && !proj_small_ok(B, H, P, h_last, w_p)) return SV_EALIGN;
   hipLaunchKernelGGL(rownorm_bwd_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, demb, emb, ynorm, B, P, dy);
   SV_LAUNCH_CHECK();
-  if (proj_small_ok(B, H, P, h_last, w_p) && !proj_tiles_ok(B, H, P, h_last, w_p, dy)) {
+  if (!tiles) {
     const int ncb = (H + 63) / 64, ndh = (B + PJ_R - 1) / PJ_R * ncb, ndw = (P + 7) / 8 * ncb;
     const size_t lds = std::max((size_t)PJ_R * P + 4 * PJ_R * 64, (size_t)B * 8 + 4 * 8 * 64) * sizeof(float);
     hipLaunchKernelGGL(proj_bwd_small_kernel, dim3(ndh + ndw), dim3(256), lds, stream, dy, h_last, B, H, P, w_p, dw_p,
@@ -237,23 +292,14 @@ extern "C" int sv_proj_norm_bwd(const float* demb, const float* emb, const float
     SV_LAUNCH_CHECK();
     return SV_OK;
   }
-  if (proj_tiles_ok(B, H, P, h_last, w_p, dy)) {
-    const int th = (H + 63) / 64, ndw = (P + 63) / 64 * th, ndh = (B + 63) / 64 * th;
-    const int ndb = (P + PB_DBW_COLS - 1) / PB_DBW_COLS;
-    constexpr size_t lds = 2 * SV_BK * (TileLd<false, 64>::value + TileLd<false, 64>::value) * sizeof(float);
-    static_assert(2 * SV_BK * (TileLd<true, 64>::value + TileLd<false, 64>::value) * sizeof(float) <= lds, "lds");
-    hipLaunchKernelGGL(proj_bwd_tiles_kernel, dim3(ndw + ndh + ndb), dim3(256), lds, stream, dy, h_last, B, H, P, w_p,
-                       dw_p, db_p, dh_last, ndw, ndh);
-    SV_LAUNCH_CHECK();
-    return SV_OK;
-  }
-  // dWp [P,H] = dy^T h_last  (A = dy as [K=B][M=P], B = h_last as [K=B][N=H])
-  int rc = gemm_f32(0, 0, P, H, B, dy, P, h_last, H, dw_p, H, nullptr, nullptr, 0.f, gws, stream, true);
-  if (rc) return rc;
-  rc = sv_colsum(dy, B, P, db_p, gws, stream);
-  if (rc) return rc;
-  // dh_last [B,H] = dy Wp  (A = dy [B, K=P] k-contig, B = Wp as [K=P][N=H])
-  return gemm_f32(1, 0, B, H, P, dy, P, w_p, H, dh_last, H, nullptr, nullptr, 0.f, gws, stream, true);
+  const int th = (H + 63) / 64, ndw = (P + 63) / 64 * th, ndh = (B + 63) / 64 * th;
+  const int ndb = (P + PB_DBW_COLS - 1) / PB_DBW_COLS;
+  constexpr size_t lds = 2 * SV_BK * (TileLd<false, 64>::value + TileLd<false, 64>::value) * sizeof(float);
+  static_assert(2 * SV_BK * (TileLd<true, 64>::value + TileLd<false, 64>::value) * sizeof(float) <= lds, "lds");
+  hipLaunchKernelGGL(proj_bwd_tiles_kernel, dim3(ndw + ndh + ndb), dim3(256), lds, stream, dy, h_last, B, H, P, w_p,
+                     dw_p, db_p, dh_last, ndw, ndh);
+  SV_LAUNCH_CHECK();
+  return SV_OK;
 }
 
 // ---------------------------------------------------------------------------

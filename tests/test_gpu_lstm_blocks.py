@@ -411,6 +411,85 @@ def test_stack_persist_vs_per_step():
         assert d <= FACTOR * max(d_ref, FLOOR), (k, d, d_ref)
 
 
+def _timing_events(n):
+    """n timing events with their native event materialised (as bench.py creates its probes)."""
+    evs = [torch.cuda.Event(enable_timing=True) for _ in range(n)]
+    for e in evs:
+        e.record()
+    return evs
+
+
+INSTRUMENTED_CASES = [(PER_STEP_CASES[0], "per_step"), (PERSIST_CASES[0], "persist")]
+
+
+@pytest.mark.parametrize("case,schedule", INSTRUMENTED_CASES, ids=["per_step.B9T37", "persist.B9T3"])
+def test_stack_bwd_instrumented(case, schedule):
+    """The stack backward's optional arguments -- timing probes, K3 stamps, grad_ready -- index the
+    event, probe and stamp arrays per layer / chunk / step; no other test passes them.  Per-step
+    (B = 9, T = 37: two chunks of PIPELINE_CHUNK = 32, the second ragged) and persistent (T = 3):
+      * grad_ready: the projection (k = L) first -- with no event under per-step, behind the stack
+        call with an event under persist -- then k = L-1 .. 0, each with an event; a clone of the
+        group's gradients taken on another stream behind that event equals their final value;
+      * every gradient is bit-identical to the uninstrumented call's (_stack_gpu; each schedule
+        reproduced itself bit for bit when run twice on an MI355X);
+      * every probe pair (2 L nch per-step, 2 L persist) measures a finite time >= 0;
+      * per-step: every (l, t) stamp pair was written, start != -1 and end >= start; persist (the
+        stamp tensor is passed there too, so the check means something): no stamp is touched."""
+    from pytorch_speaker_verification_amd import ops
+    (dims, B, T), L = case, case[0][2]
+    persist = schedule == "persist"
+    if persist:
+        _need_persist(B)
+    sd, x, demb, _ = _stack_ref(dims, B, T)
+    ps = [_dev(sd[k]) for k in _names(L)]
+    layers = [tuple(ps[4 * l:4 * l + 4]) for l in range(L)]
+    nch = (T + ops.PIPELINE_CHUNK - 1) // ops.PIPELINE_CHUNK
+    assert persist or nch == 2
+    probe = _timing_events(2 * L if persist else 2 * L * nch)
+    kstamp = torch.zeros(2 * L * T, dtype=torch.int64, device=DEV)
+    kstamp[0::2] = -1
+    grads = [torch.empty_like(t) for t in ps]
+    main = torch.cuda.current_stream()
+    calls, clones = [], {}
+
+    def grad_ready(k, event):
+        calls.append((k, event is not None))
+        group = grads[4 * L:] if k == L else grads[4 * k:4 * k + 4]
+        s = torch.cuda.Stream()
+        if event is None:
+            s.wait_stream(main)
+        else:
+            s.wait_event(event)
+        with torch.cuda.stream(s):
+            clones[k] = [g.clone() for g in group]
+
+    emb, st = ops.embedder_forward(_dev(x), layers, ps[4 * L], ps[4 * L + 1], schedule=schedule)
+    out = ops.embedder_backward(st, _dev(demb), layers, ps[4 * L], grads=grads, need_dx=False, grad_ready=grad_ready,
+                                probe=probe, kstamp=kstamp, schedule=schedule)
+    torch.cuda.synchronize()
+    ops.check_persistent_status(wait=True)
+    assert all(a is b for a, b in zip(out, grads))
+    assert calls == [(L, persist)] + [(l, True) for l in range(L - 1, -1, -1)], calls
+    for k, group in clones.items():
+        final = grads[4 * L:] if k == L else grads[4 * k:4 * k + 4]
+        for i, (c, g) in enumerate(zip(group, final)):
+            assert torch.equal(c, g), f"group {k} tensor {i}: the clone behind its event is not the final gradient"
+    plain = _stack_gpu(dims, B, T, schedule)
+    assert np.array_equal(_np(emb), plain["emb"])
+    for k, g in zip(_names(L), grads):
+        assert np.array_equal(_np(g), plain["grads"][k]), f"{k} differs from the uninstrumented call"
+    for i in range(len(probe) // 2):
+        ms = probe[2 * i].elapsed_time(probe[2 * i + 1])
+        assert np.isfinite(ms) and ms >= 0, (i, ms)
+    ks = kstamp.cpu().view(L, T, 2)
+    if persist:
+        assert (ks[..., 0] == -1).all() and (ks[..., 1] == 0).all(), "the persistent schedule wrote a stamp"
+    else:
+        assert (ks[..., 0] != -1).all(), "an (l, t) stamp pair was not written"
+        assert (ks[..., 1] >= ks[..., 0]).all()
+        print(f"\nMEASURED stack_bwd_instrumented K3 span {float((ks[..., 1] - ks[..., 0]).float().mean()) / 100:.1f} us")
+
+
 # ------------------------------------------------------------------------- 4. projection head
 def _proj_ref(dt, h, w, b, demb):
     h, w, demb = h.astype(dt), w.astype(dt), demb.astype(dt)
@@ -465,7 +544,7 @@ def test_proj_norm(B, H, P, bias):
     """sv_proj_norm_fwd / _bwd against fp64: y = h W^T + b, ynorm = |y|, emb = y / ynorm, and with
     dy = (demb - emb <demb, emb>) / ynorm: dw_p = dy^T h, db_p = sum dy, dh_last = dy W.
 
-    Forward branch by shape (proj_norm_fused / plan_gemm in sv_lstm.hip: the fused form needs
+    Forward branch by shape (proj_norm_fused / plan_gemm in sv_gemm_f32.hip: the fused form needs
     P <= 256, P % 4 == 0, no exact 256-row tiling, and a split-K plan of 2..8 slabs, which the
     `fine` plan gives from K = H >= 256 on):
       (64, 768, 256), (300, 768, 256)        fused split-K (6 slabs of K = 128) + row norm
@@ -475,7 +554,7 @@ def test_proj_norm(B, H, P, bias):
       P % 4 == 0: (9, 96, 24), (64, 768, 256), (300, 768, 256)   proj_bwd_tiles_kernel
       P % 4 != 0, B <= 128: (5, 64, 6), (128, 64, 6)             proj_bwd_small_kernel (128 = its
                                                                  upper row edge)
-      the GEMM fallback: see test_proj_norm_out_of_range.
+      neither (SV_EALIGN): see test_proj_norm_out_of_range.
     b_p = NULL once on each forward branch."""
     h, w, b, demb = _proj_inputs(B, H, P, bias)
     r64, r32 = _proj_ref(np.float64, h, w, b, demb), _proj_ref(np.float32, h, w, b, demb)
@@ -486,16 +565,15 @@ def test_proj_norm(B, H, P, bias):
 
 
 def test_proj_norm_out_of_range():
-    """(130, 64, 6): B > 128 with P % 4 != 0 fits neither backward kernel and falls to the GEMM
-    fallback, whose operand-alignment check rejects P % 4 != 0 (measured: the forward, GEMM +
-    rownorm_fwd_kernel, is within tolerance; the backward returns SV_EALIGN).  The contract either
-    way: a negative SV_E* return (call raises) or results within tolerance -- never return 0 with
-    wrong values.
+    """(130, 64, 6): B > 128 with P % 4 != 0 fits neither backward kernel, and sv_proj_norm_bwd
+    returns SV_EALIGN for what fits neither (measured: the forward, GEMM + rownorm_fwd_kernel, is
+    within tolerance; the backward returns SV_EALIGN).  The contract either way: a negative SV_E*
+    return (call raises) or results within tolerance -- never return 0 with wrong values.
 
-    From reading sv_proj_norm_bwd, the fallback never returns 0: it is reached only when
-    proj_tiles_ok fails, i.e. P % 4 != 0 or H % 4 != 0 (its first GEMM's M = P / N = H alignment
-    check) or a misaligned dy / h_last (that GEMM's pointer check) or a misaligned w_p alone (the
-    last GEMM's pointer check) -- SV_EALIGN every time."""
+    A three-GEMM fallback once stood behind the two kernels; it could never return 0 either: it was
+    reached only when proj_tiles_ok failed, i.e. P % 4 != 0 or H % 4 != 0 (its first GEMM's M = P /
+    N = H alignment check) or a misaligned dy / h_last (that GEMM's pointer check) or a misaligned
+    w_p alone (the last GEMM's pointer check) -- SV_EALIGN every time."""
     B, H, P = 130, 64, 6
     h, w, b, demb = _proj_inputs(B, H, P)
     r64, r32 = _proj_ref(np.float64, h, w, b, demb), _proj_ref(np.float32, h, w, b, demb)
