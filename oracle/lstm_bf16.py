@@ -50,29 +50,34 @@ def _params(params, L, device="cpu"):
     return layers, f("projection.weight"), f("projection.bias")
 
 
-def embedder_forward(params, x, L, bf16=True, device="cpu"):
-    """x [B,T,F] -> (emb [B,P], cache)."""
+def embedder_forward(params, x, L, bf16=True, device="cpu", tap=None):
+    """x [B,T,F] -> (emb [B,P], cache).  tap (optional; None changes nothing): a callable
+    ``tap(name, l, t, value) -> value`` through which the step's intermediates pass -- "xp" (the
+    stored x-projection [B,T,4H], t = None), "hq" (the recurrent GEMM's operand q(h_{t-1})),
+    "c_prev", "z" (the pre-activation) -- so a caller can record them (gpu_state below) or seed a
+    defect (tests/test_bf16_stepwise_verifier.py)."""
+    tp = tap if tap is not None else (lambda name, l, t, v: v)
     q = q_bf16 if bf16 else _ident
     layers, Wp, bp = _params(params, L, device)
     inp = torch.as_tensor(x, dtype=torch.float32, device=device)
     B, T, _ = inp.shape
     z = dict(device=device)
     caches = []
-    for (Wih, Whh, bih, bhh) in layers:
+    for l, (Wih, Whh, bih, bhh) in enumerate(layers):
         H = Whh.shape[1]
         qWih, qWhh = q(Wih), q(Whh)
         xq = q(inp)
-        gx = q((xq.reshape(B * T, -1) @ qWih.T).reshape(B, T, 4 * H) + (bih + bhh))
+        gx = tp("xp", l, None, q((xq.reshape(B * T, -1) @ qWih.T).reshape(B, T, 4 * H) + (bih + bhh)))
         h = torch.zeros(B, H, **z)
         c = torch.zeros(B, H, **z)
         hs = torch.empty(B, T, H, **z)
         cs = torch.empty(B, T, H, **z)
         acts = torch.empty(B, T, 4 * H, **z)
         for t in range(T):
-            g = gx[:, t] + q(h) @ qWhh.T
+            g = tp("z", l, t, gx[:, t] + tp("hq", l, t, q(h)) @ qWhh.T)
             i, f, gg, o = (torch.sigmoid(g[:, :H]), torch.sigmoid(g[:, H:2 * H]), torch.tanh(g[:, 2 * H:3 * H]),
                            torch.sigmoid(g[:, 3 * H:]))
-            c = f * c + i * gg
+            c = f * tp("c_prev", l, t, c) + i * gg
             h = o * torch.tanh(c)
             hs[:, t], cs[:, t] = h, c
             acts[:, t] = q(torch.cat([i, f, gg, o], dim=1))
@@ -84,8 +89,11 @@ def embedder_forward(params, x, L, bf16=True, device="cpu"):
     return y / n, (caches, last, y, n)
 
 
-def embedder_backward(params, demb, cache, L, bf16=True, device="cpu"):
-    """Gradients (dict keyed like params, fp32 tensors) given d emb [B,P]."""
+def embedder_backward(params, demb, cache, L, bf16=True, device="cpu", tap=None):
+    """Gradients (dict keyed like params, fp32 tensors) given d emb [B,P].  tap: as
+    embedder_forward's; here "c_prev_bwd" (the forget gate's c_{t-1}), "dGq" (a layer's stored
+    q(dG) [B,T,4H], t = None) and "dx" (its dG q(W_ih) [B,T,F_l], t = None)."""
+    tp = tap if tap is not None else (lambda name, l, t, v: v)
     q = q_bf16 if bf16 else _ident
     layers, Wp, _ = _params(params, L, device)
     caches, last, y, n = cache
@@ -107,7 +115,7 @@ def embedder_backward(params, demb, cache, L, bf16=True, device="cpu"):
         for t in range(T - 1, -1, -1):
             i, f, g, o = (acts[:, t, k * H:(k + 1) * H] for k in range(4))
             c = cs[:, t]
-            c_prev = cs[:, t - 1] if t > 0 else torch.zeros(B, H, **z)
+            c_prev = tp("c_prev_bwd", l, t, cs[:, t - 1] if t > 0 else torch.zeros(B, H, **z))
             dh = dhs[:, t] + dh_next
             tc = torch.tanh(c)
             dc = dc_next + dh * o * (1 - tc * tc)
@@ -116,6 +124,7 @@ def embedder_backward(params, demb, cache, L, bf16=True, device="cpu"):
             dGq[:, t] = q(dG)
             dh_next = dGq[:, t] @ qWhh
             dc_next = dc * f
+        dGq = tp("dGq", l, None, dGq)
         hprev = torch.cat([torch.zeros(B, 1, H, **z), q(hs[:, :-1])], dim=1)
         dG2 = dGq.reshape(B * T, 4 * H)
         grads[f"LSTM_stack.weight_ih_l{l}"] = dG2.T @ xq.reshape(B * T, -1)
@@ -123,9 +132,55 @@ def embedder_backward(params, demb, cache, L, bf16=True, device="cpu"):
         db = dG2.sum(dim=0)
         grads[f"LSTM_stack.bias_ih_l{l}"] = db
         grads[f"LSTM_stack.bias_hh_l{l}"] = db.clone()
-        dhs = (dG2 @ qWih).reshape(B, T, -1)
+        dhs = tp("dx", l, None, (dG2 @ qWih).reshape(B, T, -1))
     grads["input"] = dhs  # d loss / d x [B, T, F]: layer 0's dx_t = q(dG_t) q(W_ih)
     return grads
+
+
+def gpu_state(params, x, demb, L, tap=None, device="cpu"):
+    """The bf16-mode forward and backward of x [B,T,F] / demb [B,P] with everything the HIP bf16
+    path leaves behind, in its layouts (include/sv_ge2e.h; time-major, Bp = B rounded up to 8,
+    bf16-valued arrays as fp32): per layer lists ``xp`` [T,B,4H] (the stored x-projection),
+    ``gates`` [T,B,4H], ``c_tm`` [T,B,H], ``h_tm`` / ``h_bf`` [T+1,B,H] (slot 0 zero), ``hT``
+    [H,(T+1)Bp], ``dg`` [T,B,4H], ``dgT`` [4H,T*Bp], ``dx`` [T,B,F_l]; ``x_bf`` [T,B,F], ``xT0``
+    [F,T*Bp], ``emb``, ``grads`` (embedder_backward's dict).  tap: a further hook (a seeded defect),
+    applied before the values are recorded.  A stand-in for GPU state in the CPU self-test of
+    oracle/bf16_stepwise.py: torch fp32 sums, another order than fp64."""
+    rec = {}
+
+    def both(name, l, t, v):
+        if tap is not None:
+            v = tap(name, l, t, v)
+        if t is None:
+            rec[(name, l)] = v
+        return v
+
+    emb, cache = embedder_forward(params, x, L, True, device, tap=both)
+    grads = embedder_backward(params, demb, cache, L, True, device, tap=both)
+    caches = cache[0]
+    B, T, _ = caches[0][0].shape
+    Bp = (B + 7) // 8 * 8
+    tm = lambda a: a.transpose(0, 1).contiguous()  # noqa: E731  [B,T,*] -> [T,B,*]
+
+    def colT(a):  # [T,B,C] -> [C, T*Bp], padding columns zero
+        out = torch.zeros(a.shape[2], a.shape[0], Bp, device=a.device)
+        out[:, :, :B] = a.permute(2, 0, 1)
+        return out.reshape(a.shape[2], -1)
+
+    st = dict(B=B, T=T, Bp=Bp, emb=emb, grads=grads, x_bf=tm(caches[0][0]), xT0=colT(tm(caches[0][0])),
+              h_last=cache[1], xp=[], gates=[], c_tm=[], h_tm=[], h_bf=[], hT=[], dg=[], dgT=[], dx=[])
+    for l, (_, hs, cs, acts) in enumerate(caches):
+        h_tm = torch.cat([torch.zeros_like(hs[:, :1]), hs], dim=1)
+        st["xp"].append(tm(rec[("xp", l)]))
+        st["gates"].append(tm(acts))
+        st["c_tm"].append(tm(cs))
+        st["h_tm"].append(tm(h_tm))
+        st["h_bf"].append(q_bf16(tm(h_tm)))
+        st["hT"].append(colT(st["h_bf"][l]))
+        st["dg"].append(tm(rec[("dGq", l)]))
+        st["dgT"].append(colT(st["dg"][l]))
+        st["dx"].append(tm(rec[("dx", l)]))
+    return st
 
 
 def train_step(params, w, b, x, N, M, L, bf16=True, lr=0.01, device="cpu"):

@@ -433,6 +433,11 @@ __global__ __launch_bounds__(256, 1) void lstm_persist2_fwd_bf16_kernel(const bf
       }
       pk[0] = pack_bf2(ho[0], ho[1]);
       pk[1] = pack_bf2(ho[2], ho[3]);
+      if constexpr (XF > 0) {
+        // rows past B see the biases of the in-kernel projection, so their h is not zero (with the
+        // K1 GEMM their pre-activation, hence h, is exactly zero): keep hT's padding columns zero
+        if (b0 + b >= B) pk[0] = pk[1] = 0u;
+      }
 #pragma unroll
       for (int v = 0; v < 4; ++v) hts[(u4 + v) * LDT + b] = (bf16_t)(pk[v >> 1] >> (16 * (v & 1)));
       *reinterpret_cast<uint2*>(hsb + b * LDB + u4) = uint2{pk[0], pk[1]};

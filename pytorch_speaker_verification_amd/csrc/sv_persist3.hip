@@ -562,6 +562,11 @@ __global__ __launch_bounds__(256, 1) void lstm_persist3_fwd_bf16_kernel(
         ho[v0] = h.x;
         ho[v1] = h.y;
         pk[vp] = pack_bf2(h.x, h.y);
+        if constexpr (XF > 0) {
+          // rows past B see the biases of the in-kernel projection, so their h is not zero (with
+          // the K1 GEMM their pre-activation, hence h, is exactly zero): keep hT's padding zero
+          if (b0 + b >= Bv) pk[vp] = 0u;
+        }
         const bf16_t e0 = (bf16_t)pk[vp], e1 = (bf16_t)(pk[vp] >> 16);
         if (k == 0) {
           hk0[vp] = pk[vp];

@@ -254,6 +254,9 @@ __device__ __forceinline__ void w3_run(const WaveFwd2Args& a, int l, int ub, int
       }
       pk[0] = pack_bf2(ho[0], ho[1]);
       pk[1] = pack_bf2(ho[2], ho[3]);
+      // rows past B see the biases of the in-kernel projection, so their h is not zero: zero it
+      // here, the 16-B hT chunks below reach into the padding columns [B, Bp), which stay zero
+      if (gb >= B) pk[0] = pk[1] = 0u;
 #pragma unroll
       for (int v = 0; v < 4; ++v) hts[(u4 + v) * WV_LDT + brow] = (bf16_t)(pk[v >> 1] >> (16 * (v & 1)));
       *reinterpret_cast<uint2*>(hsb + brow * WV_LDB + u4) = uint2{pk[0], pk[1]};
