@@ -403,6 +403,34 @@ int sv_dvector_embed_bf16(int B, int T, int F, int H, int L, const float* x, con
                           const float* w_p, const float* b_p, int P, float* emb, void* workspace,
                           hipStream_t stream);
 
+/* ---- log-mel front end (added under v12; additive): a ragged batch of waveform segments to
+ * log-mel frames in one launch (librosa.stft(center=True, pad_mode='reflect') -> |.|^2 -> mel ->
+ * log10(. + 1e-6): data_preprocess.py:41-47, dvector_create.py:38-47).
+ *   y          all segments back to back, fp32
+ *   seg_off    [n_seg + 1] sample offsets into y (device int32)
+ *   frame_off  [n_seg + 1] frame offsets into out (device int32); segment s has 1 + len_s / hop
+ *              frames and frame_off[n_seg] == n_frames (the host computes both arrays)
+ *   wbasis     [win][ld_wbasis] fp32, the periodic Hann window w (length win, centred in nfft:
+ *              lpad = (nfft - win) / 2) folded into the real-DFT basis, bins k = 0 .. nfft / 2:
+ *                column 2k     = w[j] cos(2 pi k (j + lpad) / nfft)
+ *                column 2k + 1 = w[j] sin(2 pi k (j + lpad) / nfft)
+ *              nfft + 2 <= ld_wbasis <= 2^20, a multiple of 4
+ *   melfb      [nmels][nfft / 2 + 1] fp32, dense
+ *   out        [n_frames][nmels] fp32, time-major: out[f][i] = log10(sum_k melfb[i][k] P[f][k] + 1e-6),
+ *              P[f][k] = |sum_j wbasis-row-j terms of frame f|^2; frame f of a segment covers the
+ *              reflect-padded samples [f hop, f hop + nfft)
+ * One fused kernel (frames x wbasis on the exact fp32 MFMA, power, mel and log10 in its epilogue;
+ * the spectrum never goes to memory).  Limits: nfft even, 2 <= nfft <= 1024, 1 <= win <= nfft,
+ * hop >= 1, 1 <= nmels <= 128 (else SV_ESHAPE); y, wbasis, melfb, out 16-byte aligned (SV_EALIGN).
+ * Every segment must hold at least nfft / 2 + 1 samples (one reflection); the lengths live on the
+ * device, so that check is the caller's (features.logmel raises ValueError) -- the kernel clamps
+ * every sample index into its own segment, so a shorter segment gives meaningless frames but never
+ * a read outside it.  Needs no scratch: sv_logmel_workspace returns 0 and workspace may be NULL. */
+size_t sv_logmel_workspace(int n_frames, int nfft, int win, int nmels);
+int sv_logmel(const float* y, const int* seg_off, const int* frame_off, int n_seg, int n_frames, int nfft, int win,
+              int hop, int nmels, const float* wbasis, long ld_wbasis, const float* melfb, float* out,
+              void* workspace, hipStream_t stream);
+
 /* ---- clip_grad_norm_ + SGD step over one flat parameter group (train_speech_embedder.py:63-65)
  * p -= lr * min(1, max_norm / (|g|_2 + 1e-6)) * g; write_grad=1 also scales g in place.
  * sync (may be NULL): a persistent-recurrence sync block; if its status is set the step is

@@ -1,0 +1,296 @@
+// Log-mel front end (sv_logmel of the C ABI): a ragged batch of waveform segments to log-mel
+// frames [n_frames][nmels] in one launch.
+//   kernel   logmel_kernel: a workgroup (4 waves) takes 64 consecutive frames of the batch (they may
+//            belong to several segments; every frame row carries its own segment's bounds, so a row
+//            never reads a neighbouring segment) and computes
+//              S^T [bin][frame] = wbasis^T [bin][tap] x frames^T [tap][frame]
+//            on v_mfma_f32_32x32x2_f32 (exact fp32 products, a tap-ordered fmaf chain per element).
+//            Both operands are staged in LDS LM_KC taps at a time, double-buffered, the next chunk's
+//            global loads in flight during the current chunk's MFMAs: the A operand is LM_KC rows of
+//            wbasis (L2-resident; a lane's cos and sin of one bin are one 8-byte LDS read), the B
+//            operand the frames, reflect-indexed from the waveform.  The transposed orientation
+//            leaves the accumulators [bin][frame] with the frame on the lane, so the power spectrum
+//            P = re^2 + im^2 is the B operand of the mel product
+//              out^T [mel][frame] = melfb [mel][bin] x P [bin][frame]
+//            as it stands: no LDS round trip and no spectrum in memory.  log10(. + 1e-6) and a
+//            transpose through LDS finish the tile's [64][nmels] rows, which are contiguous in out.
+//   bins     the DC bin's sine column is identically zero, so its slot carries the Nyquist bin's
+//            cosine column: nfft / 2 bin pairs instead of nfft / 2 + 1 (256 at nfft = 512: 8 whole
+//            tiles of 32, all held in one pass of accumulators; nfft = 1024 takes two passes)
+//   order    every output element's sums run in a fixed order that does not depend on the frame's
+//            row in its tile, so a segment's frames are bit-identical alone or in a batch
+#include "sv_common.h"
+#include "../../include/sv_ge2e.h"
+
+namespace {
+
+constexpr int LM_BM = 64;                   // frames per workgroup
+constexpr int LM_KC = 8;                    // taps per staged chunk (16 measured the same)
+constexpr int LM_FT = LM_BM * LM_KC / 256;  // frames a thread stages per chunk
+constexpr int LM_FS = 256 / LM_KC;          // their spacing
+constexpr int LM_FLD = LM_BM + 1;           // row stride of a staged frame chunk [tap][frame]
+constexpr int LM_PASS = 256;                // bins per pass: 2 wave groups x 4 tiles of 32
+constexpr int LM_BLD = 2 * LM_PASS;         // row stride of a staged basis chunk [tap][cos, sin of 256 bins]
+constexpr int LM_BT = LM_KC * LM_BLD / 4 / 256;  // 16-byte pieces of it a thread stages per chunk
+constexpr int LM_MT = 4;                    // at most 4 mel tiles of 32 rows (nmels <= 128)
+
+// NMT: mel tiles of 32 rows, (nmels + 31) / 32
+template <int NMT>
+__global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ y, const int* __restrict__ seg_off,
+                                                     const int* __restrict__ frame_off, int n_seg, int n_frames,
+                                                     int nfft, int win, int hop, int nmels,
+                                                     const float* __restrict__ wb, int ldw,
+                                                     const float* __restrict__ melfb, float* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) float Bs[2 * LM_KC * LM_BLD];  // basis chunks; after the last chunk `red`
+  __shared__ float Fs[2 * LM_KC * LM_FLD];                               // frame chunks
+  __shared__ int rows[3 * LM_BM];  // per frame row: its segment's sample offset and length, its tap 0's sample index
+  float* red = Bs;                 // cross-wave mel sums [2][NMT][16][64], then the output tile [64][nmels]
+  static_assert(2 * LM_MT * 16 * 64 <= 2 * LM_KC * LM_BLD, "red fits in Bs");
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l31 = lane & 31, h = lane >> 5;
+  const int fh = w & 1, bg = w >> 1;  // the wave's frame half and bin group (4 tiles of 32 bins)
+  const int g0 = blockIdx.x * LM_BM;
+  const int nh = nfft / 2, nb = nh + 1, lpad = (nfft - win) / 2;
+
+  if (tid < LM_BM) {
+    const int g = g0 + tid;
+    int y0 = 0, n = 1, base = 0;  // rows past n_frames read y[0]; their columns are never stored
+    if (g < n_frames) {
+      int lo = 0, hi = n_seg - 1;  // the last segment whose first frame is <= g
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (frame_off[mid] <= g) lo = mid; else hi = mid - 1;
+      }
+      y0 = seg_off[lo];
+      n = seg_off[lo + 1] - y0;
+      base = (g - frame_off[lo]) * hop + lpad - nh;  // sample index of tap 0 before reflection
+    }
+    rows[tid] = y0;
+    rows[LM_BM + tid] = n;
+    rows[2 * LM_BM + tid] = base;
+  }
+  __syncthreads();
+
+  // Staging is branch-free: every load is clamped into its segment / table and what lies outside
+  // (a tap past the window, a column past the bins) is zeroed by a select -- at the LDS store, after
+  // the chunk's MFMAs, so that nothing waits for the loads before them.
+  // frames: thread -> tap tid % LM_KC of frames tid / LM_KC + LM_FS i
+  const int tap_l = tid & (LM_KC - 1);
+  int ry0[LM_FT], rn[LM_FT], rbase[LM_FT];
+#pragma unroll
+  for (int i = 0; i < LM_FT; ++i) {
+    const int f = tid / LM_KC + LM_FS * i;
+    ry0[i] = rows[f];
+    rn[i] = rows[LM_BM + f];
+    rbase[i] = rows[2 * LM_BM + f];
+  }
+  auto gather = [&](int c, float (&fv)[LM_FT]) {
+    const int tap = c * LM_KC + tap_l;
+#pragma unroll
+    for (int i = 0; i < LM_FT; ++i) {
+      int idx = rbase[i] + tap;
+      idx = idx < 0 ? -idx : idx;
+      idx = idx >= rn[i] ? 2 * (rn[i] - 1) - idx : idx;
+      idx = min(max(idx, 0), rn[i] - 1);  // (a segment shorter than nfft / 2 + 1 stays inside itself)
+      fv[i] = y[(long)ry0[i] + idx];
+    }
+  };
+  auto stage = [&](int c, const float (&fv)[LM_FT]) {
+    const bool on = c * LM_KC + tap_l < win;
+#pragma unroll
+    for (int i = 0; i < LM_FT; ++i)
+      Fs[((c & 1) * LM_KC + tap_l) * LM_FLD + tid / LM_KC + LM_FS * i] = on ? fv[i] : 0.f;
+  };
+  // basis: thread -> 16-byte piece tid % 128 of rows tid / 128 + 2 i of the pass's 512 columns
+  const int bcol = 4 * (tid & 127), brow = tid >> 7;
+  // (bn: Nyquist's cosine, for DC's sine slot in column 1)
+  auto load_basis = [&](int c, int pass, f32x4 (&bv)[LM_BT], float (&bn)[LM_BT]) {
+    const int col = pass * LM_BLD + bcol;
+#pragma unroll
+    for (int i = 0; i < LM_BT; ++i) {
+      const int tap = c * LM_KC + brow + 2 * i;
+      const unsigned roff = (unsigned)min(tap, win - 1) * (unsigned)ldw;
+      bv[i] = *reinterpret_cast<const f32x4*>(wb + (roff + (unsigned)min(col, ldw - 4)));
+      bn[i] = wb[roff + (unsigned)nfft];
+    }
+  };
+  auto stage_basis = [&](int c, int pass, const f32x4 (&bv)[LM_BT], const float (&bn)[LM_BT]) {
+    const int col = pass * LM_BLD + bcol;
+#pragma unroll
+    for (int i = 0; i < LM_BT; ++i) {
+      const bool on = c * LM_KC + brow + 2 * i < win && col < nfft;
+      f32x4 v = bv[i];
+      v[1] = col == 0 ? bn[i] : v[1];
+      *reinterpret_cast<f32x4*>(&Bs[((c & 1) * LM_KC + brow + 2 * i) * LM_BLD + bcol]) =
+          on ? v : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  };
+
+  f32x16 macc[NMT];
+#pragma unroll
+  for (int mt = 0; mt < NMT; ++mt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) macc[mt][r] = 0.f;
+
+  const int nchunk = (win + LM_KC - 1) / LM_KC;
+  const int npass = (nh + LM_PASS - 1) / LM_PASS;
+  for (int pass = 0; pass < npass; ++pass) {
+    const int bin0 = pass * LM_PASS + bg * 128;               // the wave's first bin of this pass
+    const int ntile = min(4, max(0, (nh - bin0 + 31) / 32));  // its tiles that hold bins (wave-uniform)
+    const bool nyq = bin0 == 0;                               // tile 0 holds DC (and Nyquist in its sine slot)
+    f32x16 are[4], aim[4];
+#pragma unroll
+    for (int bt = 0; bt < 4; ++bt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) are[bt][r] = aim[bt][r] = 0.f;
+
+    float fv[LM_FT], bn[LM_BT];
+    f32x4 bv[LM_BT];
+    gather(0, fv);
+    load_basis(0, pass, bv, bn);
+    __syncthreads();  // (the previous pass's reads of the stages are done)
+    stage(0, fv);
+    stage_basis(0, pass, bv, bn);
+    __syncthreads();
+    for (int c = 0; c < nchunk; ++c) {
+      const int cur = c & 1;
+      const bool more = c + 1 < nchunk;
+      if (more) {
+        gather(c + 1, fv);
+        load_basis(c + 1, pass, bv, bn);
+      }
+      // a wave or tile without bins multiplies zeros (it has its own SIMD and would otherwise wait
+      // at the barrier): the loop stays straight-line
+      const float* F = Fs + cur * LM_KC * LM_FLD + 32 * fh + l31;
+      const float* B = Bs + cur * LM_KC * LM_BLD + 2 * (bg * 128 + l31);
+      // the chunk's operands first, then its MFMAs
+      float f[LM_KC / 2];
+      float2 b[LM_KC / 2][4];
+#pragma unroll
+      for (int ks = 0; ks < LM_KC / 2; ++ks) {
+        f[ks] = F[(2 * ks + h) * LM_FLD];
+#pragma unroll
+        for (int bt = 0; bt < 4; ++bt)
+          b[ks][bt] = *reinterpret_cast<const float2*>(B + (2 * ks + h) * LM_BLD + 64 * bt);
+      }
+#pragma unroll
+      for (int ks = 0; ks < LM_KC / 2; ++ks)
+#pragma unroll
+        for (int bt = 0; bt < 4; ++bt) {
+          are[bt] = mfma32x32x2(b[ks][bt].x, f[ks], are[bt]);
+          aim[bt] = mfma32x32x2(b[ks][bt].y, f[ks], aim[bt]);
+        }
+      if (more) {
+        stage(c + 1, fv);
+        stage_basis(c + 1, pass, bv, bn);
+      }
+      __syncthreads();
+    }
+
+    // power and mel: accumulator r of lane (l31, h) is bin (tile base + acc_row(r, lane)) of frame
+    // l31, which is P [k = h][j = l31] of the k pair (b_r, b_r + 4), b_r = acc_row(r, 0)
+    // The mel weights of a (tile, mel tile) are loaded as a batch before its 16 MFMAs, masked by a
+    // multiply (a select lets the compiler move each load into a branch of its own, one L2 round
+    // trip per MFMA); every load is clamped into the table
+#pragma unroll
+    for (int bt = 0; bt < 4; ++bt) {
+      if (bt >= ntile) continue;
+      const int tb = bin0 + 32 * bt;
+      float p[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float re = are[bt][r], im = aim[bt][r];
+        const bool dc = nyq && bt == 0 && r == 0 && h == 0;  // DC: its sine slot is Nyquist's cosine
+        p[r] = dc ? re * re : re * re + im * im;
+      }
+#pragma unroll
+      for (int mt = 0; mt < NMT; ++mt) {
+        const int m = 32 * mt + l31;
+        const float* wrow = melfb + (long)min(m, nmels - 1) * nb;
+        const float mrow = m < nmels ? 1.f : 0.f;
+        float wv[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int bin = tb + acc_row(r, lane);
+          wv[r] = wrow[min(bin, nh - 1)] * (bin < nh ? mrow : 0.f);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) macc[mt] = mfma32x32x2(wv[r], p[r], macc[mt]);
+      }
+      if (bt == 0 && nyq) {  // the Nyquist bin: k = 0 of one more k pair, k = 1 empty
+        const float im = aim[0][0];
+        const float pn = h == 0 ? im * im : 0.f;
+#pragma unroll
+        for (int mt = 0; mt < NMT; ++mt) {
+          const int m = 32 * mt + l31;
+          const float wl = melfb[(long)min(m, nmels - 1) * nb + nh] * ((m < nmels && h == 0) ? 1.f : 0.f);
+          macc[mt] = mfma32x32x2(wl, pn, macc[mt]);
+        }
+      }
+    }
+  }
+
+  // sum the two bin groups of each frame half (group 0 + group 1), log10, transpose through LDS
+  if (bg == 1) {
+#pragma unroll
+    for (int mt = 0; mt < NMT; ++mt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) red[((fh * NMT + mt) * 16 + r) * 64 + lane] = macc[mt][r];
+  }
+  __syncthreads();
+  if (bg == 0) {
+#pragma unroll
+    for (int mt = 0; mt < NMT; ++mt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) macc[mt][r] += red[((fh * NMT + mt) * 16 + r) * 64 + lane];
+  }
+  __syncthreads();
+  if (bg == 0) {
+#pragma unroll
+    for (int mt = 0; mt < NMT; ++mt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int m = 32 * mt + acc_row(r, lane);
+        if (m < nmels) red[(32 * fh + l31) * nmels + m] = log10f(macc[mt][r] + 1e-6f);
+      }
+  }
+  __syncthreads();
+  const int nvalid = min(LM_BM, n_frames - g0) * nmels;
+  float* dst = out + (long)g0 * nmels;
+  for (int i = tid; i < nvalid; i += 256) dst[i] = red[i];
+}
+
+}  // namespace
+
+extern "C" size_t sv_logmel_workspace(int n_frames, int nfft, int win, int nmels) {
+  (void)n_frames, (void)nfft, (void)win, (void)nmels;
+  return 0;  // the fused kernel keeps the spectrum in registers
+}
+
+extern "C" int sv_logmel(const float* y, const int* seg_off, const int* frame_off, int n_seg, int n_frames, int nfft,
+                         int win, int hop, int nmels, const float* wbasis, long ld_wbasis, const float* melfb,
+                         float* out, void* workspace, hipStream_t stream) {
+  (void)workspace;
+  if (!y || !seg_off || !frame_off || !wbasis || !melfb || !out || n_seg < 1 || n_frames < n_seg) return SV_EARG;
+  if (nfft < 2 || nfft > 1024 || nfft % 2 || win < 1 || win > nfft || hop < 1 || nmels < 1 || nmels > 32 * LM_MT)
+    return SV_ESHAPE;
+  if (ld_wbasis < nfft + 2) return SV_EARG;
+  if (ld_wbasis % 4 || (((uintptr_t)y | (uintptr_t)wbasis | (uintptr_t)melfb | (uintptr_t)out) & 15) ||
+      (((uintptr_t)seg_off | (uintptr_t)frame_off) & 3))
+    return SV_EALIGN;
+  if (ld_wbasis > (1L << 20)) return SV_EARG;  // (the kernel indexes the table with 32-bit offsets)
+  const int nmt = (nmels + 31) / 32, ldw = (int)ld_wbasis;
+  const dim3 grid((n_frames + LM_BM - 1) / LM_BM);
+#define LM_LAUNCH(NMT)                                                                                       \
+  hipLaunchKernelGGL(logmel_kernel<NMT>, grid, dim3(256), 0, stream, y, seg_off, frame_off, n_seg, n_frames, \
+                     nfft, win, hop, nmels, wbasis, ldw, melfb, out)
+  switch (nmt) {
+    case 1: LM_LAUNCH(1); break;
+    case 2: LM_LAUNCH(2); break;
+    case 3: LM_LAUNCH(3); break;
+    default: LM_LAUNCH(4); break;
+  }
+#undef LM_LAUNCH
+  SV_LAUNCH_CHECK();
+  return SV_OK;
+}

@@ -3,9 +3,10 @@
 The reference turns each VAD-concatenated segment's log-mel spectrogram [nmels, T] into
 24-frame windows at a 12-frame hop (0.24 s / 0.12 s, :48-52), embeds all windows with the
 SpeechEmbedder (:100) and averages consecutive window embeddings into ~0.4 s segments
-(align_embeddings, :55-73).  Audio I/O, VAD (webrtcvad) and the STFT (librosa) stay out of
-scope; this module starts from the log-mel frames.  The embedding is the short-sequence,
-large-batch forward of the same HIP LSTM kernels (T = 24).
+(align_embeddings, :55-73).  Audio I/O and VAD (webrtcvad) stay out of scope; embed_segments
+starts from a file's waveform segments (features.logmel is the STFT / log-mel front end), the
+rest of the module from the log-mel frames.  The embedding is the short-sequence, large-batch
+forward of the same HIP LSTM kernels (T = 24).
 """
 from __future__ import annotations
 
@@ -29,6 +30,24 @@ def window_frames(logmel, win=WIN, hop=HOP):
     if not starts:
         return np.zeros((0, win, logmel.shape[0]), dtype=np.float32)
     return np.stack([logmel[:, j:j + win].T for j in starts]).astype(np.float32)
+
+
+def window_index(frame_off, win=WIN, hop=HOP):
+    """Row indices [S, win] into time-major log-mel frames [n_frames, nmels] (features.logmel) of
+    every segment's windows: per segment of T_s frames, starts j = 0, hop, ... while j + win < T_s
+    (window_frames' rule, dvector_create.py:49), segments in order."""
+    starts = [a + j for a, b in zip(frame_off[:-1], frame_off[1:]) for j in range(0, b - a, hop) if j + win < b - a]
+    return np.asarray(starts, dtype=np.int64).reshape(-1, 1) + np.arange(win, dtype=np.int64)[None, :]
+
+
+def windows_from_logmel(out, frame_off, win=WIN, hop=HOP):
+    """[n_frames, nmels] time-major log-mel frames of a ragged batch (features.logmel) -> the
+    windows [S, win, nmels] of all its segments, on out's device: one gather with a host-built
+    index table (window_index)."""
+    idx = window_index(frame_off, win, hop)
+    if idx.shape[0] == 0:
+        return out.new_zeros((0, win, out.shape[1]))
+    return out[torch.from_numpy(idx).to(out.device)]
 
 
 def dvec_ok(F, H):
@@ -182,3 +201,19 @@ def align_embeddings(embeddings):
     for i, (a, b) in enumerate(parts):
         out[i] = np.average(e[a:b], axis=0)
     return out
+
+
+def embed_segments(net, segs, precision="f32", **kw):
+    """Aligned d-vectors [n_aligned, proj] float64 of one file's concatenated VAD segments (a list
+    of 1-D waveforms at hp.data.sr): dvector_create.py:97-101 -- get_STFTs, embedder_net(windows),
+    align_embeddings -- as features.logmel -> windows_from_logmel -> embed_windows on the device
+    tensor (no host round trip) -> align_embeddings.  No window at all (every segment too short for
+    one) gives an empty [0, proj] array.  **kw goes to embed_windows."""
+    from .features import logmel
+    out, frame_off = logmel(segs)
+    windows = windows_from_logmel(out, frame_off)
+    proj = net.projection.weight.shape[0]
+    if windows.shape[0] == 0:
+        return np.zeros((0, proj))
+    emb = embed_windows(net, windows, precision=precision, **kw)
+    return align_embeddings(emb.cpu().numpy())
