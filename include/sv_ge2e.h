@@ -431,6 +431,26 @@ int sv_logmel(const float* y, const int* seg_off, const int* frame_off, int n_se
               int hop, int nmels, const float* wbasis, long ld_wbasis, const float* melfb, float* out,
               void* workspace, hipStream_t stream);
 
+/* ---- framed energy (added under v12; additive): the per-sample half of librosa.effects.split /
+ * trim (data_preprocess.py:35), feature.rms(center=True, pad_mode='reflect') ** 2, for a ragged
+ * batch of waveforms in one launch.  y, seg_off, frame_off, n_seg, n_frames as in sv_logmel:
+ * packed fp32 samples, device int32 tables of n_seg + 1 entries, waveform s has 1 + len_s / hop
+ * frames and frame_off[n_seg] == n_frames.
+ *   mse        [n_frames] fp32: mse[f] = (1 / frame_length) sum_j y[r(f hop - frame_length / 2 + j)]^2,
+ *              j = 0 .. frame_length - 1, f counted within the waveform, r(i) = -i for i < 0,
+ *              2 (len - 1) - i for i >= len (one reflection), then clamped into the waveform
+ * One wave per frame: fp32 squares and partial sums in an order that depends on j alone (a
+ * waveform's mse is bit-identical alone or in a batch), one multiply by 1 / frame_length.  No
+ * workspace, nothing allocated or retained.  The dB threshold against each waveform's own maximum
+ * and the interval bookkeeping are the host's (features.split).  Limits: frame_length even,
+ * 2 <= frame_length <= 2^20, hop >= 1 (else SV_ESHAPE); y and mse 16-byte aligned, the tables 4-byte
+ * (SV_EALIGN); null pointers, n_seg < 1 or n_frames < n_seg are SV_EARG.  Every waveform must hold
+ * at least frame_length / 2 + 1 samples; as for sv_logmel that check is the caller's
+ * (features.frame_energy raises ValueError) and a shorter one never reads outside itself (an empty
+ * one reads nothing and gives 0). */
+int sv_frame_energy(const float* y, const int* seg_off, const int* frame_off, int n_seg, int n_frames,
+                    int frame_length, int hop, float* mse, hipStream_t stream);
+
 /* ---- clip_grad_norm_ + SGD step over one flat parameter group (train_speech_embedder.py:63-65)
  * p -= lr * min(1, max_norm / (|g|_2 + 1e-6)) * g; write_grad=1 also scales g in place.
  * sync (may be NULL): a persistent-recurrence sync block; if its status is set the step is

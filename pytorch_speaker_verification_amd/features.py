@@ -1,5 +1,6 @@
-"""Log-mel front end on the GPU: waveform segments -> log-mel frames (reference
-data_preprocess.py:38-47 and dvector_create.get_STFTs, :38-47).
+"""Offline preprocessing on the GPU: waveforms -> voiced intervals -> log-mel frames -> the
+``speakerN.npy`` training tensors (reference data_preprocess.py:24-54 and
+dvector_create.get_STFTs, :38-47).
 
 The function is the reference's ``librosa.stft(center=True, pad_mode='reflect')`` -> ``|.|**2`` ->
 ``librosa.filters.mel`` (Slaney scale, area-normalised) -> ``log10(. + 1e-6)``, written out from its
@@ -9,11 +10,20 @@ DFT basis) on the exact fp32 MFMA, power, mel and log10 in its epilogue.  The ou
 ``[n_frames, nmels]``, so a d-vector window is a row slice and a ``[nmels, T]`` training slice is a
 transposed row slice.
 
-Audio decoding, resampling, VAD (webrtcvad), ``librosa.effects.split`` / ``trim`` and the
-magnitude-dB feature of ``utils.mfccs_and_spec`` stay out of scope: this module starts from mono
-fp32 samples at ``hp.data.sr``.
+``split`` / ``trim`` are ``librosa.effects.split`` / ``trim`` of librosa < 0.10 (the versions the
+reference's positional calls work with; ``feature.rms`` pads with ``pad_mode='reflect'`` there),
+written out from their definition: the framed energy of a ragged batch of waveforms is one launch
+of the HIP kernel ``sv_frame_energy``; the dB threshold against each waveform's own maximum and the
+edges are numpy on the host.  ``preprocess_speaker`` is the body of data_preprocess.py:30-49 on
+decoded waveforms (one ``split``, one ``logmel``, one gather) and ``save_speakers`` its 90/10 writer.
+
+Audio decoding, resampling, VAD (webrtcvad) and the magnitude-dB feature of
+``utils.mfccs_and_spec`` stay out of scope: this module starts from mono fp32 samples at
+``hp.data.sr``.
 """
 from __future__ import annotations
+
+import os
 
 import numpy as np
 import torch
@@ -178,3 +188,173 @@ def preprocess_utterance(utter, intervals, tisv_frame=None):
         specs.append(np.ascontiguousarray(S[:, :tisv_frame], dtype=np.float32))
         specs.append(np.ascontiguousarray(S[:, -tisv_frame:], dtype=np.float32))
     return specs
+
+
+def _pack(segs, seg_off, frame_off):
+    """(y, seg_off, frame_off, device) on the GPU, as logmel packs them: host segments and both
+    offset tables in one pinned buffer and one copy; device-resident segments concatenated there."""
+    on_dev = [s for s in segs if torch.is_tensor(s) and s.is_cuda]
+    dev = on_dev[0].device if on_dev else _lib.compute_device(torch.empty(0))
+    n, n_seg = int(seg_off[-1]), len(segs)
+    offs = np.concatenate([seg_off, frame_off])
+    if on_dev:
+        y = torch.cat([torch.as_tensor(s).to(dev, torch.float32) for s in segs]) if n_seg > 1 else \
+            on_dev[0].to(torch.float32).contiguous()
+        if y.data_ptr() % 16:  # a slice of a larger tensor: the entry points want 16-byte alignment
+            y = y.clone()
+        o = torch.from_numpy(offs).to(dev)
+    else:
+        npad = (n + 3) // 4 * 4
+        host = torch.empty(npad + offs.size, dtype=torch.float32, pin_memory=True)
+        hn = host.numpy()
+        for s, a in zip(segs, seg_off[:-1]):
+            hn[a:a + s.shape[0]] = s.numpy() if torch.is_tensor(s) else np.asarray(s)
+        hn[n:npad] = 0.0
+        hn[npad:].view(np.int32)[:] = offs
+        buf = host.to(dev, non_blocking=True)
+        y, o = buf[:n], buf[npad:].view(torch.int32)
+    return y, o[:n_seg + 1], o[n_seg + 1:], dev
+
+
+def energy_offsets(lengths, frame_length, hop_length):
+    """(seg_off, frame_off) int32 arrays of len + 1 for waveforms of `lengths` samples: waveform s
+    holds 1 + len_s // hop_length energy frames.  ValueError for an odd frame_length, a hop below 1
+    or a waveform shorter than frame_length // 2 + 1 samples (one reflection at each end)."""
+    if frame_length < 2 or frame_length % 2 or frame_length > 2 ** 20 or hop_length < 1:
+        raise ValueError(f"unsupported framing: frame_length={frame_length} (even, 2 .. 2**20), hop_length={hop_length} "
+                         "(>= 1)")
+    lengths = np.asarray(lengths, dtype=np.int64)
+    if lengths.size == 0:
+        raise ValueError("frame_energy needs at least one waveform")
+    short = np.nonzero(lengths < frame_length // 2 + 1)[0]
+    if short.size:
+        raise ValueError(f"waveform {int(short[0])} has {int(lengths[short[0]])} samples; reflect padding of "
+                         f"frame_length={frame_length} needs at least {frame_length // 2 + 1}")
+    seg_off = np.concatenate([[0], np.cumsum(lengths)])
+    frame_off = np.concatenate([[0], np.cumsum(1 + lengths // hop_length)])
+    if seg_off[-1] >= 2 ** 31:
+        raise ValueError("too many samples for one frame_energy call (32-bit offsets): split the batch")
+    return seg_off.astype(np.int32), frame_off.astype(np.int32)
+
+
+def frame_energy(waves, frame_length=2048, hop_length=512):
+    """Mean square of every centred, reflect-padded frame (librosa.feature.rms ** 2) of one waveform
+    or a list of them (1-D arrays or tensors, host or device): (mse [n_frames] cuda float32,
+    frame_off) with waveform s in mse[frame_off[s] : frame_off[s + 1]].  One packed copy in and one
+    kernel launch for the whole batch; a waveform's values do not depend on its neighbours."""
+    segs = _as_list(waves)
+    for s in segs:
+        if getattr(s, "ndim", None) != 1:
+            raise ValueError("each waveform must be a 1-D array or tensor of samples")
+    seg_off, frame_off = energy_offsets([int(s.shape[0]) for s in segs], frame_length, hop_length)
+    y, so, fo, dev = _pack(segs, seg_off, frame_off)
+    n_frames = int(frame_off[-1])
+    mse = torch.empty(n_frames, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        frame_energy_into(y, so, fo, len(segs), n_frames, frame_length, hop_length, mse)
+    return mse, [int(v) for v in frame_off]
+
+
+def frame_energy_into(y, seg_off, frame_off, n_seg, n_frames, frame_length, hop_length, mse):
+    """sv_frame_energy on device tensors (y fp32, offsets int32, mse [>= n_frames] fp32)."""
+    _lib.call("sv_frame_energy", _lib.ptr(y), _lib.ptr(seg_off), _lib.ptr(frame_off), n_seg, n_frames, frame_length,
+              hop_length, _lib.ptr(mse), _lib.stream_of(mse))
+
+
+def intervals_from_energy(mse, n, hop_length, top_db=60, amin=1e-10):
+    """The host half of split: the frames of one waveform of n samples whose power is within top_db
+    of the waveform's loudest frame (10 log10(max(amin, mse)), a strict comparison), as [k, 2] int64
+    sample intervals [start, end) -- frame edges times hop_length, capped at n."""
+    mse = np.asarray(mse, dtype=np.float64)
+    db = 10.0 * np.log10(np.maximum(amin, mse)) - 10.0 * np.log10(max(amin, float(mse.max())))
+    nonsilent = db > -top_db
+    edges = np.flatnonzero(np.diff(nonsilent.astype(np.int8), prepend=0, append=0))
+    return np.minimum(edges.astype(np.int64) * hop_length, n).reshape(-1, 2)
+
+
+def split(waves, top_db=60, frame_length=2048, hop_length=512):
+    """librosa.effects.split: the non-silent [start, end) sample intervals of one waveform ([k, 2]
+    int64, k may be 0) or of each waveform of a list (a list of such arrays).  Every waveform is
+    measured against its own loudest frame.  One launch and one device-to-host copy per call."""
+    segs = _as_list(waves)
+    mse, frame_off = frame_energy(segs, frame_length, hop_length)
+    mse = mse.cpu().numpy()
+    out = [intervals_from_energy(mse[a:b], int(s.shape[0]), hop_length, top_db)
+           for s, a, b in zip(segs, frame_off[:-1], frame_off[1:])]
+    return out if isinstance(waves, (list, tuple)) else out[0]
+
+
+def trim(wave, top_db=60, frame_length=2048, hop_length=512):
+    """librosa.effects.trim: (wave[start:end], (start, end)) from the first non-silent interval's
+    start to the last one's end; (0, 0) if no frame is non-silent."""
+    iv = split(wave, top_db, frame_length, hop_length)
+    start, end = (int(iv[0, 0]), int(iv[-1, 1])) if len(iv) else (0, 0)
+    return wave[start:end], (start, end)
+
+
+def preprocess_speaker(utterances, top_db=30, tisv_frame=None):
+    """The body of data_preprocess.py:30-49 for one speaker's decoded utterances (1-D waveforms at
+    hp.data.sr): float32 [K, nmels, tisv_frame], for every utterance in order and every non-silent
+    interval of split(utter, top_db) in order that is longer than (tisv_frame * hop + window) * sr
+    samples, the first and then the last tisv_frame frames of that part's log-mel
+    (np.array(utterances_spec)).  No kept interval gives shape (0, nmels, tisv_frame), where the
+    reference would save an array of shape (0,).  Utterances too short to hold such an interval
+    are skipped before the split.
+
+    One split call over all utterances, one logmel call over all kept parts, one gather on the
+    device, one copy out.  Only what is kept is computed: of a part with more than
+    2 tisv_frame + 3 frames, logmel sees a head that ends nfft / 2 samples after the last kept
+    frame's centre and a tail that starts on a hop multiple at least nfft / 2 samples before the
+    first kept frame's centre; each kept frame reads exactly the samples it reads in the whole part,
+    so by sv_logmel's order guarantee the result is bit-identical to the whole part's."""
+    tisv = hp.data.tisv_frame if tisv_frame is None else tisv_frame
+    _, nfft, _, hop_n, nmels = _config(None, None, None, None, None)
+    utter_min_len = (tisv * hp.data.hop + hp.data.window) * hp.data.sr
+    # an utterance of at most utter_min_len samples has no interval longer than that: not split at all
+    # (nor refused for being shorter than split's reflect padding)
+    utterances = [u for u in utterances if getattr(u, "ndim", None) != 1 or u.shape[0] > utter_min_len]
+    if not utterances:
+        return np.zeros((0, nmels, tisv), dtype=np.float32)
+    lead = -(-(nfft // 2) // hop_n)  # frames of a tail before its first frame free of the cut's reflection
+    segs, picks = [], []  # segments for logmel; (segment, first frame) of every [tisv] slice
+    for utter, intervals in zip(utterances, split(utterances, top_db=top_db)):
+        for a, b in intervals:
+            a, b = int(a), int(b)
+            if not (b - a) > utter_min_len:
+                continue
+            part = utter[a:b]
+            T = 1 + (b - a) // hop_n
+            if T > 2 * tisv + 3:
+                picks += [(len(segs), 0), (len(segs) + 1, lead)]
+                segs += [part[:(tisv - 1) * hop_n + nfft // 2], part[(T - tisv - lead) * hop_n:]]
+            else:
+                picks += [(len(segs), 0), (len(segs), T - tisv)]
+                segs.append(part)
+    if not segs:
+        return np.zeros((0, nmels, tisv), dtype=np.float32)
+    if len(segs) == 1 and torch.is_tensor(segs[0]) and segs[0].is_cuda:
+        segs[0] = segs[0].clone()  # (a lone device-resident slice: logmel takes it as it is, aligned or not)
+    out, frame_off = logmel(segs)
+    rows = np.array([frame_off[s] + f for s, f in picks], dtype=np.int64)[:, None] + np.arange(tisv)[None, :]
+    spec = out[torch.from_numpy(rows).to(out.device)].transpose(1, 2).contiguous()  # [K, nmels, tisv]
+    return spec.cpu().numpy().astype(np.float32, copy=False)
+
+
+def save_speakers(speakers, train_path, test_path, top_db=30):
+    """data_preprocess.py:24-27, 51-54 on decoded audio: `speakers` is a sequence of utterance lists;
+    the first (len // 10) * 9 go to train_path/speaker%d.npy, the rest to test_path/speaker%d.npy
+    renumbered from 0, each as preprocess_speaker(utterances, top_db).  Makes both directories.
+    Returns (train files, test files)."""
+    os.makedirs(train_path, exist_ok=True)
+    os.makedirs(test_path, exist_ok=True)
+    train_speaker_num = (len(speakers) // 10) * 9
+    written = ([], [])
+    for i, utterances in enumerate(speakers):
+        spec = preprocess_speaker(utterances, top_db=top_db)
+        if i < train_speaker_num:
+            path = os.path.join(train_path, "speaker%d.npy" % i)
+        else:
+            path = os.path.join(test_path, "speaker%d.npy" % (i - train_speaker_num))
+        np.save(path, spec)
+        written[i >= train_speaker_num].append(path)
+    return written
