@@ -431,6 +431,41 @@ int sv_logmel(const float* y, const int* seg_off, const int* frame_off, int n_se
               int hop, int nmels, const float* wbasis, long ld_wbasis, const float* melfb, float* out,
               void* workspace, hipStream_t stream);
 
+/* ---- mel magnitude in dB (added under v12; additive): the raw-waveform training feature of
+ * utils.mfccs_and_spec(wav_process=True) (utils.py:138-158) for a ragged batch of virtual segments:
+ * librosa.stft(center=True, pad_mode='reflect') -> |.| -> mel -> amplitude_to_db (ref 1, amin,
+ * top_db), time-major.  wbasis, ld_wbasis, melfb, frame_off, n_seg, n_frames and the limits as in
+ * sv_logmel.  Instead of seg_off, three device int32 arrays of n_seg entries describe segment s as
+ * the virtual signal z[i] = i < seg_valid[s] ? y[seg_start[s] + i] : 0, i = 0 .. seg_len[s] - 1:
+ *   seg_start  the segment's first sample in y
+ *   seg_valid  how many real samples follow it (0 <= seg_valid; seg_start + max(seg_valid, 1) must
+ *              lie inside y: with seg_valid = 0 the kernel still loads y[seg_start], and drops it)
+ *   seg_len    the virtual length L_s; the segment has 1 + L_s / hop frames and the STFT's
+ *              reflection is taken against L_s, so librosa.effects.trim (a start and a count),
+ *              librosa.util.fix_length's zero padding (seg_valid < L_s) and its truncation
+ *              (seg_valid = L_s < the count) are index arithmetic: y is never copied or re-packed.
+ *              L_s >= nfft / 2 + 1 is the caller's check, as for sv_logmel (a shorter segment gives
+ *              meaningless frames, never a read outside its real samples).  Segments may overlap in y.
+ *   out        [n_frames][nmels] fp32: with x[f][i] = sum_k melfb[i][k] |STFT[f][k]|,
+ *              db[f][i] = 20 log10(max(amin, x[f][i])), and for top_db >= 0
+ *              out[f][i] = max(db[f][i], 20 log10(max(amin, seg_max[s])) - top_db), s the segment of
+ *              f; top_db < 0: no clip, out = db
+ *   seg_max    [n_seg] fp32, output: the largest x of the segment's frames (>= 0)
+ * The fused kernel of sv_logmel in a second instantiation (magnitude in place of power as the mel
+ * product's operand; IEEE sqrt, no fast-math), whose epilogue folds every valid frame row's largest
+ * x into seg_max[its segment] with an unsigned integer atomic max on the float's bits (exact and
+ * independent of order for x >= 0; seg_max is zeroed on the stream first), then one elementwise
+ * kernel for the clip.  A segment's out and seg_max are bit-identical alone or in any batch.  No
+ * host synchronisation, no allocation, graph-capturable; sv_meldb_workspace returns 0 and workspace
+ * may be NULL.  Errors as sv_logmel, plus SV_EARG for amin <= 0 (or NaN) and a null seg_max, and
+ * SV_EALIGN for a seg_* / seg_max pointer off a 4-byte boundary; all checks return before any
+ * launch. */
+size_t sv_meldb_workspace(int n_frames, int nfft, int win, int nmels);
+int sv_meldb(const float* y, const int* seg_start, const int* seg_valid, const int* seg_len, const int* frame_off,
+             int n_seg, int n_frames, int nfft, int win, int hop, int nmels, const float* wbasis, long ld_wbasis,
+             const float* melfb, float amin, float top_db, float* out, float* seg_max, void* workspace,
+             hipStream_t stream);
+
 /* ---- framed energy (added under v12; additive): the per-sample half of librosa.effects.split /
  * trim (data_preprocess.py:35), feature.rms(center=True, pad_mode='reflect') ** 2, for a ragged
  * batch of waveforms in one launch.  y, seg_off, frame_off, n_seg, n_frames as in sv_logmel:

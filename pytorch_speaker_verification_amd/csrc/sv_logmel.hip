@@ -19,6 +19,14 @@
 //            tiles of 32, all held in one pass of accumulators; nfft = 1024 takes two passes)
 //   order    every output element's sums run in a fixed order that does not depend on the frame's
 //            row in its tile, so a segment's frames are bit-identical alone or in a batch
+// Magnitude / dB mode (sv_meldb of the C ABI, the same kernel's second instantiation): a segment is
+// a virtual signal (seg_start, seg_valid, seg_len) -- seg_valid samples of y from seg_start, then
+// zeros up to seg_len, reflected against seg_len -- so trim, zero padding and truncation are index
+// arithmetic on the one uploaded buffer.  The spectrum's magnitude sqrt(re^2 + im^2) takes the
+// power's place as the mel product's operand; the epilogue writes 20 log10(max(x, amin)) and folds
+// the raw mel sums x of every valid frame row into seg_max[its segment] by an unsigned integer
+// atomic max on the float's bits (x >= 0: exact, and independent of the order of arrival).
+// meldb_clip_kernel then lifts every element to its own segment's maximum - top_db.
 #include "sv_common.h"
 #include "../../include/sv_ge2e.h"
 
@@ -34,16 +42,27 @@ constexpr int LM_BLD = 2 * LM_PASS;         // row stride of a staged basis chun
 constexpr int LM_BT = LM_KC * LM_BLD / 4 / 256;  // 16-byte pieces of it a thread stages per chunk
 constexpr int LM_MT = 4;                    // at most 4 mel tiles of 32 rows (nmels <= 128)
 
+constexpr int LM_POWER = 0;  // |.|^2, log10(. + 1e-6); segments from seg_off (sv_logmel)
+constexpr int LM_MAGDB = 1;  // |.|, 20 log10(max(., amin)), per-segment maximum; virtual segments (sv_meldb)
+
 // NMT: mel tiles of 32 rows, (nmels + 31) / 32
-template <int NMT>
+// MODE: LM_POWER (seg_off [n_seg + 1]; seg_valid, seg_len, amin, seg_max unused) or LM_MAGDB
+//       (seg_off is seg_start [n_seg])
+template <int NMT, int MODE>
 __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ y, const int* __restrict__ seg_off,
                                                      const int* __restrict__ frame_off, int n_seg, int n_frames,
                                                      int nfft, int win, int hop, int nmels,
                                                      const float* __restrict__ wb, int ldw,
-                                                     const float* __restrict__ melfb, float* __restrict__ out) {
+                                                     const float* __restrict__ melfb, float* __restrict__ out,
+                                                     const int* __restrict__ seg_valid,
+                                                     const int* __restrict__ seg_len, float amin,
+                                                     unsigned* __restrict__ seg_max) {
+  constexpr bool MAG = MODE == LM_MAGDB;
   __shared__ __attribute__((aligned(16))) float Bs[2 * LM_KC * LM_BLD];  // basis chunks; after the last chunk `red`
   __shared__ float Fs[2 * LM_KC * LM_FLD];                               // frame chunks
-  __shared__ int rows[3 * LM_BM];  // per frame row: its segment's sample offset and length, its tap 0's sample index
+  // per frame row: its segment's sample offset and length, its tap 0's sample index; MAG: also the
+  // segment's count of real samples and its index
+  __shared__ int rows[(MAG ? 5 : 3) * LM_BM];
   float* red = Bs;                 // cross-wave mel sums [2][NMT][16][64], then the output tile [64][nmels]
   static_assert(2 * LM_MT * 16 * 64 <= 2 * LM_KC * LM_BLD, "red fits in Bs");
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -55,6 +74,7 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ y
   if (tid < LM_BM) {
     const int g = g0 + tid;
     int y0 = 0, n = 1, base = 0;  // rows past n_frames read y[0]; their columns are never stored
+    int nv = 0, sg = 0;
     if (g < n_frames) {
       int lo = 0, hi = n_seg - 1;  // the last segment whose first frame is <= g
       while (lo < hi) {
@@ -62,12 +82,22 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ y
         if (frame_off[mid] <= g) lo = mid; else hi = mid - 1;
       }
       y0 = seg_off[lo];
-      n = seg_off[lo + 1] - y0;
+      if constexpr (MAG) {
+        n = seg_len[lo];
+        nv = seg_valid[lo];
+        sg = lo;
+      } else {
+        n = seg_off[lo + 1] - y0;
+      }
       base = (g - frame_off[lo]) * hop + lpad - nh;  // sample index of tap 0 before reflection
     }
     rows[tid] = y0;
     rows[LM_BM + tid] = n;
     rows[2 * LM_BM + tid] = base;
+    if constexpr (MAG) {
+      rows[3 * LM_BM + tid] = nv;
+      rows[4 * LM_BM + tid] = sg;
+    }
   }
   __syncthreads();
 
@@ -76,30 +106,41 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ y
   // the chunk's MFMAs, so that nothing waits for the loads before them.
   // frames: thread -> tap tid % LM_KC of frames tid / LM_KC + LM_FS i
   const int tap_l = tid & (LM_KC - 1);
-  int ry0[LM_FT], rn[LM_FT], rbase[LM_FT];
+  int ry0[LM_FT], rn[LM_FT], rbase[LM_FT], rv[MAG ? LM_FT : 1];
 #pragma unroll
   for (int i = 0; i < LM_FT; ++i) {
     const int f = tid / LM_KC + LM_FS * i;
     ry0[i] = rows[f];
     rn[i] = rows[LM_BM + f];
     rbase[i] = rows[2 * LM_BM + f];
+    if constexpr (MAG) rv[i] = rows[3 * LM_BM + f];
   }
-  auto gather = [&](int c, float (&fv)[LM_FT]) {
+  // MAG: bit i of fz says that sample i of the chunk lies in the segment's zero padding (the load
+  // is clamped into its real samples, [0, max(valid, 1) - 1]; stage zeroes the value)
+  auto gather = [&](int c, float (&fv)[LM_FT], unsigned& fz) {
     const int tap = c * LM_KC + tap_l;
+    if constexpr (MAG) fz = 0u;
 #pragma unroll
     for (int i = 0; i < LM_FT; ++i) {
       int idx = rbase[i] + tap;
       idx = idx < 0 ? -idx : idx;
       idx = idx >= rn[i] ? 2 * (rn[i] - 1) - idx : idx;
       idx = min(max(idx, 0), rn[i] - 1);  // (a segment shorter than nfft / 2 + 1 stays inside itself)
+      if constexpr (MAG) {
+        fz |= idx >= rv[i] ? 1u << i : 0u;
+        idx = min(idx, max(rv[i], 1) - 1);
+      }
       fv[i] = y[(long)ry0[i] + idx];
     }
   };
-  auto stage = [&](int c, const float (&fv)[LM_FT]) {
+  auto stage = [&](int c, const float (&fv)[LM_FT], unsigned fz) {
     const bool on = c * LM_KC + tap_l < win;
 #pragma unroll
-    for (int i = 0; i < LM_FT; ++i)
-      Fs[((c & 1) * LM_KC + tap_l) * LM_FLD + tid / LM_KC + LM_FS * i] = on ? fv[i] : 0.f;
+    for (int i = 0; i < LM_FT; ++i) {
+      bool keep = on;
+      if constexpr (MAG) keep = on && !(fz >> i & 1u);
+      Fs[((c & 1) * LM_KC + tap_l) * LM_FLD + tid / LM_KC + LM_FS * i] = keep ? fv[i] : 0.f;
+    }
   };
   // basis: thread -> 16-byte piece tid % 128 of rows tid / 128 + 2 i of the pass's 512 columns
   const int bcol = 4 * (tid & 127), brow = tid >> 7;
@@ -146,17 +187,18 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ y
 
     float fv[LM_FT], bn[LM_BT];
     f32x4 bv[LM_BT];
-    gather(0, fv);
+    unsigned fz = 0u;
+    gather(0, fv, fz);
     load_basis(0, pass, bv, bn);
     __syncthreads();  // (the previous pass's reads of the stages are done)
-    stage(0, fv);
+    stage(0, fv, fz);
     stage_basis(0, pass, bv, bn);
     __syncthreads();
     for (int c = 0; c < nchunk; ++c) {
       const int cur = c & 1;
       const bool more = c + 1 < nchunk;
       if (more) {
-        gather(c + 1, fv);
+        gather(c + 1, fv, fz);
         load_basis(c + 1, pass, bv, bn);
       }
       // a wave or tile without bins multiplies zeros (it has its own SIMD and would otherwise wait
@@ -181,14 +223,15 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ y
           aim[bt] = mfma32x32x2(b[ks][bt].y, f[ks], aim[bt]);
         }
       if (more) {
-        stage(c + 1, fv);
+        stage(c + 1, fv, fz);
         stage_basis(c + 1, pass, bv, bn);
       }
       __syncthreads();
     }
 
-    // power and mel: accumulator r of lane (l31, h) is bin (tile base + acc_row(r, lane)) of frame
-    // l31, which is P [k = h][j = l31] of the k pair (b_r, b_r + 4), b_r = acc_row(r, 0)
+    // power (MAG: magnitude) and mel: accumulator r of lane (l31, h) is bin (tile base +
+    // acc_row(r, lane)) of frame l31, which is P [k = h][j = l31] of the k pair (b_r, b_r + 4),
+    // b_r = acc_row(r, 0)
     // The mel weights of a (tile, mel tile) are loaded as a batch before its 16 MFMAs, masked by a
     // multiply (a select lets the compiler move each load into a branch of its own, one L2 round
     // trip per MFMA); every load is clamped into the table
@@ -201,7 +244,10 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ y
       for (int r = 0; r < 16; ++r) {
         const float re = are[bt][r], im = aim[bt][r];
         const bool dc = nyq && bt == 0 && r == 0 && h == 0;  // DC: its sine slot is Nyquist's cosine
-        p[r] = dc ? re * re : re * re + im * im;
+        if constexpr (MAG)
+          p[r] = dc ? fabsf(re) : sqrtf(re * re + im * im);
+        else
+          p[r] = dc ? re * re : re * re + im * im;
       }
 #pragma unroll
       for (int mt = 0; mt < NMT; ++mt) {
@@ -219,7 +265,7 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ y
       }
       if (bt == 0 && nyq) {  // the Nyquist bin: k = 0 of one more k pair, k = 1 empty
         const float im = aim[0][0];
-        const float pn = h == 0 ? im * im : 0.f;
+        const float pn = h == 0 ? (MAG ? fabsf(im) : im * im) : 0.f;
 #pragma unroll
         for (int mt = 0; mt < NMT; ++mt) {
           const int m = 32 * mt + l31;
@@ -231,6 +277,8 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ y
   }
 
   // sum the two bin groups of each frame half (group 0 + group 1), log10, transpose through LDS
+  // (MAG: 20 log10(max(., amin)), and the largest raw sum of every frame row into its segment's
+  // seg_max)
   if (bg == 1) {
 #pragma unroll
     for (int mt = 0; mt < NMT; ++mt)
@@ -246,18 +294,69 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ y
   }
   __syncthreads();
   if (bg == 0) {
+    float rmax = 0.f;  // (the sums are >= 0)
 #pragma unroll
     for (int mt = 0; mt < NMT; ++mt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int m = 32 * mt + acc_row(r, lane);
-        if (m < nmels) red[(32 * fh + l31) * nmels + m] = log10f(macc[mt][r] + 1e-6f);
+        if constexpr (MAG) {
+          if (m < nmels) {
+            red[(32 * fh + l31) * nmels + m] = 20.f * log10f(fmaxf(macc[mt][r], amin));
+            rmax = fmaxf(rmax, macc[mt][r]);
+          }
+        } else {
+          if (m < nmels) red[(32 * fh + l31) * nmels + m] = log10f(macc[mt][r] + 1e-6f);
+        }
       }
+    if constexpr (MAG) {
+      // the lane pair (l31, h = 0 / 1) holds frame row 32 fh + l31's mels; lanes h = 0 fold.  A
+      // wave whose valid rows all belong to one segment (most do) folds them first: one atomic
+      rmax = fmaxf(rmax, __shfl_xor(rmax, 32, 64));
+      const int f = 32 * fh + l31;
+      const bool valid = h == 0 && g0 + f < n_frames;
+      const int sg = rows[4 * LM_BM + f];
+      const int sg0 = rows[4 * LM_BM + 32 * fh];  // (row 32 fh is valid if any row of the wave is)
+      const bool one = __builtin_amdgcn_ballot_w64(valid && sg != sg0) == 0;
+      if (one) {
+        const float wmax = wave_max_dpp(valid ? rmax : 0.f);
+        if (lane == 0 && g0 + f < n_frames) atomicMax(seg_max + sg0, __float_as_uint(wmax));
+      } else if (valid) {
+        atomicMax(seg_max + sg, __float_as_uint(rmax));
+      }
+    }
   }
   __syncthreads();
   const int nvalid = min(LM_BM, n_frames - g0) * nmels;
   float* dst = out + (long)g0 * nmels;
   for (int i = tid; i < nvalid; i += 256) dst[i] = red[i];
+}
+
+// out[f][:] = max(out[f][:], 20 log10(max(seg_max[segment of f], amin)) - top_db): a workgroup takes
+// the 64 frame rows of one tile of the main kernel (contiguous in out)
+__global__ __launch_bounds__(256) void meldb_clip_kernel(const int* __restrict__ frame_off, int n_seg, int n_frames,
+                                                         int nmels, const float* __restrict__ seg_max, float amin,
+                                                         float top_db, float* __restrict__ out) {
+  __shared__ float level[LM_BM];
+  const int tid = threadIdx.x;
+  const int g0 = blockIdx.x * LM_BM;
+  if (tid < LM_BM) {
+    const int g = g0 + tid;
+    float lv = 0.f;
+    if (g < n_frames) {
+      int lo = 0, hi = n_seg - 1;  // the last segment whose first frame is <= g
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (frame_off[mid] <= g) lo = mid; else hi = mid - 1;
+      }
+      lv = 20.f * log10f(fmaxf(seg_max[lo], amin)) - top_db;
+    }
+    level[tid] = lv;
+  }
+  __syncthreads();
+  const int nvalid = min(LM_BM, n_frames - g0) * nmels;
+  float* dst = out + (long)g0 * nmels;
+  for (int i = tid; i < nvalid; i += 256) dst[i] = fmaxf(dst[i], level[i / nmels]);
 }
 
 }  // namespace
@@ -282,8 +381,9 @@ extern "C" int sv_logmel(const float* y, const int* seg_off, const int* frame_of
   const int nmt = (nmels + 31) / 32, ldw = (int)ld_wbasis;
   const dim3 grid((n_frames + LM_BM - 1) / LM_BM);
 #define LM_LAUNCH(NMT)                                                                                       \
-  hipLaunchKernelGGL(logmel_kernel<NMT>, grid, dim3(256), 0, stream, y, seg_off, frame_off, n_seg, n_frames, \
-                     nfft, win, hop, nmels, wbasis, ldw, melfb, out)
+  hipLaunchKernelGGL((logmel_kernel<NMT, LM_POWER>), grid, dim3(256), 0, stream, y, seg_off, frame_off, n_seg, \
+                     n_frames, nfft, win, hop, nmels, wbasis, ldw, melfb, out, (const int*)nullptr,          \
+                     (const int*)nullptr, 0.f, (unsigned*)nullptr)
   switch (nmt) {
     case 1: LM_LAUNCH(1); break;
     case 2: LM_LAUNCH(2); break;
@@ -292,5 +392,50 @@ extern "C" int sv_logmel(const float* y, const int* seg_off, const int* frame_of
   }
 #undef LM_LAUNCH
   SV_LAUNCH_CHECK();
+  return SV_OK;
+}
+
+extern "C" size_t sv_meldb_workspace(int n_frames, int nfft, int win, int nmels) {
+  (void)n_frames, (void)nfft, (void)win, (void)nmels;
+  return 0;  // the per-segment maxima live in the caller's seg_max
+}
+
+extern "C" int sv_meldb(const float* y, const int* seg_start, const int* seg_valid, const int* seg_len,
+                        const int* frame_off, int n_seg, int n_frames, int nfft, int win, int hop, int nmels,
+                        const float* wbasis, long ld_wbasis, const float* melfb, float amin, float top_db, float* out,
+                        float* seg_max, void* workspace, hipStream_t stream) {
+  (void)workspace;
+  if (!y || !seg_start || !seg_valid || !seg_len || !frame_off || !wbasis || !melfb || !out || !seg_max || n_seg < 1 ||
+      n_frames < n_seg || !(amin > 0.f))
+    return SV_EARG;
+  if (nfft < 2 || nfft > 1024 || nfft % 2 || win < 1 || win > nfft || hop < 1 || nmels < 1 || nmels > 32 * LM_MT)
+    return SV_ESHAPE;
+  if (ld_wbasis < nfft + 2) return SV_EARG;
+  if (ld_wbasis % 4 || (((uintptr_t)y | (uintptr_t)wbasis | (uintptr_t)melfb | (uintptr_t)out) & 15) ||
+      (((uintptr_t)seg_start | (uintptr_t)seg_valid | (uintptr_t)seg_len | (uintptr_t)frame_off | (uintptr_t)seg_max) &
+       3))
+    return SV_EALIGN;
+  if (ld_wbasis > (1L << 20)) return SV_EARG;  // (the kernel indexes the table with 32-bit offsets)
+  const int nmt = (nmels + 31) / 32, ldw = (int)ld_wbasis;
+  const dim3 grid((n_frames + LM_BM - 1) / LM_BM);
+  const int rc = sv_zero_bytes(seg_max, (size_t)n_seg * sizeof(float), stream);
+  if (rc) return rc;
+  unsigned* smax = reinterpret_cast<unsigned*>(seg_max);
+#define LM_LAUNCH(NMT)                                                                                         \
+  hipLaunchKernelGGL((logmel_kernel<NMT, LM_MAGDB>), grid, dim3(256), 0, stream, y, seg_start, frame_off, n_seg, \
+                     n_frames, nfft, win, hop, nmels, wbasis, ldw, melfb, out, seg_valid, seg_len, amin, smax)
+  switch (nmt) {
+    case 1: LM_LAUNCH(1); break;
+    case 2: LM_LAUNCH(2); break;
+    case 3: LM_LAUNCH(3); break;
+    default: LM_LAUNCH(4); break;
+  }
+#undef LM_LAUNCH
+  SV_LAUNCH_CHECK();
+  if (top_db >= 0.f) {
+    hipLaunchKernelGGL(meldb_clip_kernel, grid, dim3(256), 0, stream, frame_off, n_seg, n_frames, nmels,
+                       (const float*)seg_max, amin, top_db, out);
+    SV_LAUNCH_CHECK();
+  }
   return SV_OK;
 }

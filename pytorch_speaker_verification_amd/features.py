@@ -17,9 +17,18 @@ of the HIP kernel ``sv_frame_energy``; the dB threshold against each waveform's 
 edges are numpy on the host.  ``preprocess_speaker`` is the body of data_preprocess.py:30-49 on
 decoded waveforms (one ``split``, one ``logmel``, one gather) and ``save_speakers`` its 90/10 writer.
 
-Audio decoding, resampling, VAD (webrtcvad) and the magnitude-dB feature of
-``utils.mfccs_and_spec`` stay out of scope: this module starts from mono fp32 samples at
-``hp.data.sr``.
+``mel_db`` is the raw-waveform training feature, ``mel_db`` of ``utils.mfccs_and_spec``
+(utils.py:150-158): the same STFT's magnitude -> mel -> ``librosa.amplitude_to_db`` (ref 1,
+amin 1e-5, top_db 80 against each utterance's own maximum), time-major, from the HIP entry point
+``sv_meldb``.  ``mel_db_fixed`` puts ``wav_process=True`` (utils.py:145-148) in front --
+``librosa.effects.trim(frame_length=win, hop_length=hop)`` and ``librosa.util.fix_length`` -- as
+index arithmetic on the one uploaded buffer: a batch of utterances to ``[n, T, nmels]`` in one
+``sv_frame_energy`` launch and one ``sv_meldb`` call.
+
+Audio decoding, resampling and VAD (webrtcvad) stay out of scope: this module starts from mono
+fp32 samples at ``hp.data.sr``.  So do the other two outputs of ``utils.mfccs_and_spec``:
+``mag_db`` (the reference's dataset drops it) and ``calc_mfccs`` (a DCT over the time axis of the
+already transposed array, with ``librosa.filters.dct``, which librosa removed).
 """
 from __future__ import annotations
 
@@ -290,6 +299,121 @@ def trim(wave, top_db=60, frame_length=2048, hop_length=512):
     iv = split(wave, top_db, frame_length, hop_length)
     start, end = (int(iv[0, 0]), int(iv[-1, 1])) if len(iv) else (0, 0)
     return wave[start:end], (start, end)
+
+
+def _check_db(amin, top_db):
+    if not amin > 0:
+        raise ValueError(f"amin must be positive (got {amin})")
+    if top_db is not None and top_db < 0:
+        raise ValueError(f"top_db must be non-negative or None (got {top_db})")
+    return float(amin), -1.0 if top_db is None else float(top_db)  # (a negative top_db: sv_meldb skips the clip)
+
+
+def mel_db(waves, sr=None, nfft=None, window=None, hop=None, nmels=None, amin=1e-5, top_db=80.0):
+    """Mel magnitude in dB of one waveform segment or a list of them (1-D arrays or tensors, host or
+    device, mono at `sr`): (out [n_frames, nmels] cuda float32, frame_off), a ragged batch packed
+    exactly as logmel packs one.  out = amplitude_to_db(melfb @ |stft|).T of librosa < 0.10:
+    20 log10(max(amin, .)), then nothing below the segment's own maximum - top_db (top_db=None: no
+    clip).  One packed copy in and one sv_meldb call for the whole batch; a segment's values do not
+    depend on its neighbours.  Decoding, resampling, mag_db and calc_mfccs are out of scope."""
+    sr, nfft, win, hop_n, nmels = _config(sr, nfft, window, hop, nmels)
+    amin, top_db = _check_db(amin, top_db)
+    segs = _as_list(waves)
+    for s in segs:
+        if getattr(s, "ndim", None) != 1:
+            raise ValueError("each segment must be a 1-D array or tensor of samples")
+    seg_off, frame_off = segment_offsets([int(s.shape[0]) for s in segs], nfft, hop_n)
+    n_seg, n_frames = len(segs), int(frame_off[-1])
+    # the lengths ride behind frame_off in _pack's one copy: seg_valid = seg_len = the real lengths
+    y, so, fo, dev = _pack(segs, seg_off, np.concatenate([frame_off, np.diff(seg_off)]).astype(np.int32))
+    lengths = fo[n_seg + 1:]
+    wbasis, melfb = stft_tables(sr, nfft, win, nmels, dev)
+    out = torch.empty((n_frames, nmels), dtype=torch.float32, device=dev)
+    seg_max = torch.empty(n_seg, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        mel_db_into(y, so[:n_seg], lengths, lengths, fo[:n_seg + 1], n_seg, n_frames, nfft, win, hop_n, nmels, wbasis,
+                    melfb, out, seg_max, amin, top_db)
+    return out, [int(v) for v in frame_off]
+
+
+def mel_db_into(y, seg_start, seg_valid, seg_len, frame_off, n_seg, n_frames, nfft, win, hop, nmels, wbasis, melfb, out,
+                seg_max, amin=1e-5, top_db=80.0):
+    """sv_meldb on device tensors (y fp32; seg_start, seg_valid, seg_len [n_seg] and frame_off
+    [n_seg + 1] int32; out [>= n_frames, nmels] and seg_max [>= n_seg] fp32 contiguous): segment s is
+    seg_valid[s] samples of y from seg_start[s], then zeros up to seg_len[s].  top_db < 0 or None:
+    no clip.  seg_max receives each segment's largest mel magnitude."""
+    _lib.call("sv_meldb", _lib.ptr(y), _lib.ptr(seg_start), _lib.ptr(seg_valid), _lib.ptr(seg_len), _lib.ptr(frame_off),
+              n_seg, n_frames, nfft, win, hop, nmels, _lib.ptr(wbasis), wbasis.stride(0), _lib.ptr(melfb), amin,
+              -1.0 if top_db is None else top_db, _lib.ptr(out), _lib.ptr(seg_max), None, _lib.stream_of(out))
+
+
+def fixed_length(length=None):
+    """The reference's fixed utterance length in samples, int(sr * (tisv_frame * hop + window))
+    (utils.py:142,147; 29200 at the defaults), unless `length` is given."""
+    return int(hp.data.sr * (hp.data.tisv_frame * hp.data.hop + hp.data.window)) if length is None else int(length)
+
+
+def fixed_segments(bounds, seg_off, length, hop):
+    """The segment table of mel_db_fixed as one int32 array [4 n + 1]: seg_start, seg_valid, seg_len
+    (n entries each) and frame_off (n + 1).  Waveform s sits at seg_off[s] of the packed buffer and
+    was trimmed to [a, b) = bounds[s]: fix_length(wave[a:b], length) is b - a real samples from
+    seg_off[s] + a, cut at `length` (truncation) or followed by zeros up to it (padding; an empty
+    trim has 0 real samples)."""
+    bounds = np.asarray(bounds, dtype=np.int64).reshape(-1, 2)
+    n = len(bounds)
+    start = np.asarray(seg_off, dtype=np.int64)[:n] + bounds[:, 0]
+    valid = np.minimum(bounds[:, 1] - bounds[:, 0], length)
+    frame_off = np.arange(n + 1, dtype=np.int64) * (1 + length // hop)
+    if frame_off[-1] * 128 >= 2 ** 31:
+        raise ValueError("too many frames for one mel_db_fixed call (32-bit offsets): split the batch")
+    return np.concatenate([start, valid, np.full(n, length, dtype=np.int64), frame_off]).astype(np.int32)
+
+
+def mel_db_fixed(waves, length=None, trim_top_db=60, amin=1e-5, top_db=80.0):
+    """utils.mfccs_and_spec(f, wav_process=True)[1] for every decoded waveform of a list (or one
+    waveform; 1-D arrays or tensors, host or device, mono at hp.data.sr): cuda float32
+    [n, 1 + length // hop, nmels] with hp.data's configuration, from
+    trim(wave, top_db=trim_top_db, frame_length=win, hop_length=hop) -> fix_length(., length) ->
+    mel_db.  `length` defaults to the reference's int(sr * (tisv_frame * hop + window));
+    trim_top_db=None skips the trim.
+
+    One pack and upload, one sv_frame_energy launch at (win, hop), one copy of the energies back for
+    the trim bounds (numpy, intervals_from_energy), one upload of the segment table and one sv_meldb
+    call: trim, zero padding and truncation are that table's index arithmetic, the audio is never
+    copied or re-packed on the device.  ValueError for a waveform shorter than win // 2 + 1 samples
+    (the trim's reflection) or a length below nfft // 2 + 1 (the STFT's)."""
+    sr, nfft, win, hop_n, nmels = _config(None, None, None, None, None)
+    amin, top_db = _check_db(amin, top_db)
+    length = fixed_length(length)
+    if length < nfft // 2 + 1:
+        raise ValueError(f"length={length}; reflect padding of an nfft={nfft} STFT needs at least {nfft // 2 + 1}")
+    segs = _as_list(waves)
+    for s in segs:
+        if getattr(s, "ndim", None) != 1:
+            raise ValueError("each waveform must be a 1-D array or tensor of samples")
+    lengths = [int(s.shape[0]) for s in segs]
+    seg_off, efo = energy_offsets(lengths, win, hop_n)  # (ValueError for a waveform shorter than win // 2 + 1)
+    y, so, fo, dev = _pack(segs, seg_off, efo)
+    n = len(segs)
+    with torch.cuda.device(dev):
+        if trim_top_db is None:
+            bounds = [(0, m) for m in lengths]
+        else:
+            mse = torch.empty(int(efo[-1]), dtype=torch.float32, device=dev)
+            frame_energy_into(y, so, fo, n, int(efo[-1]), win, hop_n, mse)
+            mse = mse.cpu().numpy()
+            bounds = []
+            for m, a, b in zip(lengths, efo[:-1], efo[1:]):
+                iv = intervals_from_energy(mse[a:b], m, hop_n, trim_top_db)
+                bounds.append((int(iv[0, 0]), int(iv[-1, 1])) if len(iv) else (0, 0))
+        table = torch.from_numpy(fixed_segments(bounds, seg_off, length, hop_n)).pin_memory().to(dev, non_blocking=True)
+        T = 1 + length // hop_n
+        wbasis, melfb = stft_tables(sr, nfft, win, nmels, dev)
+        out = torch.empty((n, T, nmels), dtype=torch.float32, device=dev)
+        seg_max = torch.empty(n, dtype=torch.float32, device=dev)
+        mel_db_into(y, table[:n], table[n:2 * n], table[2 * n:3 * n], table[3 * n:], n, n * T, nfft, win, hop_n, nmels,
+                    wbasis, melfb, out, seg_max, amin, top_db)
+    return out
 
 
 def preprocess_speaker(utterances, top_db=30, tisv_frame=None):

@@ -14,6 +14,10 @@
     centroids from get_centroids, get_cossim(verification, enrollment centroids), the 50-point
     threshold sweep on device (exact integer counts, sv_eer_counts) and the reference's float32
     FAR/FRR/EER selection.  Returns the average EER (the reference only prints it).
+
+Both take ``dataset=None``: a given dataset replaces the configured one -- the way to train or
+evaluate the reference's raw-waveform configuration (``data_preprocessed: false``) on decoded audio,
+with ``data_load.SpeakerDatasetWaveforms``, whose batches are made on the GPU and skip the pinned copy.
 """
 from __future__ import annotations
 
@@ -44,11 +48,18 @@ def _value_neutral_perm(n):
     return random.sample(range(0, n), n)
 
 
-def train(model_path):
+def _loader(dataset, split, pin_memory):
+    """The reference's DataLoader (:26-27 / :97); a dataset whose items are already on the device
+    (on_device) is read in this process and not pinned."""
+    on_device = getattr(dataset, "on_device", False)
+    return DataLoader(dataset, batch_size=split.N, shuffle=True, num_workers=0 if on_device else split.num_workers,
+                      drop_last=True, pin_memory=pin_memory and not on_device)
+
+
+def train(model_path, dataset=None):
     device = torch.device(hp.device)
-    train_dataset = _dataset()
-    loader = DataLoader(train_dataset, batch_size=hp.train.N, shuffle=True, num_workers=hp.train.num_workers,
-                        drop_last=True, pin_memory=True)
+    train_dataset = _dataset() if dataset is None else dataset
+    loader = _loader(train_dataset, hp.train, True)
     embedder_net = SpeechEmbedder().to(device)
     if hp.train.restore:
         embedder_net.load_state_dict(torch.load(model_path, weights_only=True))
@@ -105,11 +116,10 @@ def eer_from_sim(sim):
     return best
 
 
-def test(model_path):
+def test(model_path, dataset=None):
     device = torch.device(hp.device)
-    test_dataset = _dataset()
-    loader = DataLoader(test_dataset, batch_size=hp.test.N, shuffle=True, num_workers=hp.test.num_workers,
-                        drop_last=True)
+    test_dataset = _dataset() if dataset is None else dataset
+    loader = _loader(test_dataset, hp.test, False)
     embedder_net = SpeechEmbedder()
     embedder_net.load_state_dict(torch.load(model_path, weights_only=True))
     embedder_net = embedder_net.to(device).eval()

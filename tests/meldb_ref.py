@@ -1,0 +1,75 @@
+"""Reference mel-magnitude-in-dB feature for the tests: plain numpy, written from the definition
+(librosa < 0.10: stft(center=True, pad_mode='reflect') -> |.| -> Slaney mel filterbank ->
+amplitude_to_db(ref=1, amin=1e-5, top_db=80), time-major; with wav_process, effects.trim(top_db=60,
+frame_length=win, hop_length=hop) and util.fix_length in front).
+
+It shares no code with pytorch_speaker_verification_amd.features (the tests compare the two); the
+framing, the DFT basis, the filterbank and the signals come from logmel_ref, the trim from split_ref.
+`dtype=np.float64` is the reference; `dtype=np.float32` is the yardstick for the GPU kernel's bound:
+the same definition evaluated in fp32 on the CPU (frames x basis by a numpy fp32 matmul, then fp32
+magnitude, mel, log10, maximum and clip)."""
+import numpy as np
+
+import logmel_ref as R
+import split_ref as S
+
+AMIN = 1e-5
+TOP_DB = 80.0
+
+
+def mag_ref(z, sr=16000, nfft=512, window=0.025, hop=0.01, dtype=np.float64):
+    """|STFT| [n_frames, nfft//2 + 1] in `dtype`."""
+    win, hop_n, _ = R.sizes(sr, nfft, window, hop)
+    fr = R.frames_of(np.asarray(z, dtype=np.float64), nfft, win, hop_n).astype(dtype)
+    c, s = R.dft_basis(nfft, win)
+    re = fr @ c.astype(dtype)
+    im = fr @ s.astype(dtype)
+    return np.sqrt(re * re + im * im)
+
+
+def mel_mag_ref(z, sr=16000, nfft=512, window=0.025, hop=0.01, nmels=40, dtype=np.float64):
+    """The mel sums x [n_frames, nmels] before the dB."""
+    return mag_ref(z, sr, nfft, window, hop, dtype) @ R.mel_fb(sr, nfft, nmels).astype(dtype).T
+
+
+def db_of(x, amin=AMIN, top_db=TOP_DB):
+    """20 log10(max(amin, x)), then nothing below its own maximum - top_db (None: no clip), in x's dtype."""
+    dtype = x.dtype.type
+    db = dtype(20.0) * np.log10(np.maximum(dtype(amin), x))
+    if top_db is not None:
+        db = np.maximum(db, db.max() - dtype(top_db))
+    assert db.dtype == x.dtype
+    return db
+
+
+def meldb_ref(z, dtype=np.float64, amin=AMIN, top_db=TOP_DB, **cfg):
+    """[n_frames, nmels] (time-major) in `dtype` of one waveform z (its own maximum for the clip)."""
+    return db_of(mel_mag_ref(z, dtype=dtype, **cfg), amin, top_db)
+
+
+def fix_length(y, L):
+    """librosa.util.fix_length: zero-pad at the end or truncate to L samples."""
+    y = np.asarray(y)
+    out = np.zeros(L, dtype=y.dtype)
+    out[:min(L, len(y))] = y[:L]
+    return out
+
+
+def trim_bounds(y, trim_top_db, win=400, hop=160):
+    return (0, len(y)) if trim_top_db is None else S.trim_ref(y, trim_top_db, win, hop)
+
+
+def fixed_ref(y, L, trim_top_db=60, dtype=np.float64, **kw):
+    """mfccs_and_spec(wav_process=True)'s mel_db of a decoded waveform at the default
+    configuration: trim(frame_length=400, hop_length=160), fix_length(L), meldb_ref."""
+    a, b = trim_bounds(y, trim_top_db)
+    return meldb_ref(fix_length(np.asarray(y)[a:b], L), dtype=dtype, **kw)
+
+
+def err_bound(z, factor=6.0, **kw):
+    """(reference fp64 [n_frames, nmels], bound): bound = factor x the largest error the fp32 CPU
+    evaluation of the same definition makes against fp64 on this input (the yardstick of
+    logmel_ref.err_bound)."""
+    ref = meldb_ref(z, **kw)
+    f32 = meldb_ref(z, dtype=np.float32, **kw)
+    return ref, factor * float(np.abs(f32.astype(np.float64) - ref).max())
