@@ -486,6 +486,46 @@ int sv_meldb(const float* y, const int* seg_start, const int* seg_valid, const i
 int sv_frame_energy(const float* y, const int* seg_off, const int* frame_off, int n_seg, int n_frames,
                     int frame_length, int hop, float* mse, hipStream_t stream);
 
+/* ---- corpus d-vector export (added under v12; additive): the three device steps of
+ * dvector.embed_files, which turns the voiced ranges of many files into uis-rnn sequences
+ * (dvector_create.py:84-122) with one log-mel launch, one embedding pass and one averaging launch
+ * per batch of files.
+ *
+ * sv_logmel_ranges: sv_logmel on ranges of ONE uploaded buffer.  Instead of seg_off, two device int32
+ * arrays of n_seg entries give segment s as y[seg_start[s] .. seg_start[s] + seg_len[s]); ranges may
+ * touch, overlap or leave gaps, and y is never re-packed.  frame_off, wbasis, melfb, out, the limits,
+ * the alignment rules (the tables 4-byte), the error codes and "all checks return before any launch"
+ * as in sv_logmel.  seg_len[s] >= nfft / 2 + 1 and seg_start[s] + seg_len[s] inside y are the caller's
+ * checks (features.logmel_ranges raises ValueError); the kernel never reads outside
+ * [seg_start, seg_start + seg_len).  The fused kernel of sv_logmel in a third instantiation that
+ * differs only in where a frame row's origin and length come from: a range's frames are
+ * bit-identical to sv_logmel's of a packed copy of that range, alone or in any batch. */
+int sv_logmel_ranges(const float* y, const int* seg_start, const int* seg_len, const int* frame_off, int n_seg,
+                     int n_frames, int nfft, int win, int hop, int nmels, const float* wbasis, long ld_wbasis,
+                     const float* melfb, float* out, void* workspace, hipStream_t stream);
+
+/* sv_dvector_embed_bf16_frames: sv_dvector_embed_bf16 reading its windows in place.  Instead of x,
+ * frames [n_rows][F] fp32 (time-major log-mel rows, 16-byte aligned) and a device int32 win_start[B]:
+ * window b, step t is row win_start[b] + t, clamped into [0, n_rows - 1] (a bad table never reads
+ * outside frames).  Only the kernel that builds the padded bf16 x operand differs; the per-step
+ * kernels, the workspace (sv_dvector_bf16_workspace) and the projection are shared, so emb is
+ * bit-identical to sv_dvector_embed_bf16 on the materialised windows at the same B.  SV_EARG for a
+ * null frames / win_start or n_rows < 1, SV_EALIGN for a misaligned one, before any launch. */
+int sv_dvector_embed_bf16_frames(int B, int T, int F, int H, int L, const float* frames, int n_rows,
+                                 const int* win_start, const float* const* w_ih, const float* const* w_hh,
+                                 const float* const* b_ih, const float* const* b_hh, const float* w_p,
+                                 const float* b_p, int P, float* emb, void* workspace, hipStream_t stream);
+
+/* sv_dvec_align: align_embeddings (dvector_create.py:55-73) of a batch of files in one launch.
+ * emb [S][P] fp32; part_off [n_parts + 1] device int32 row offsets (dvector.partitions per file,
+ * concatenated over the files); out [n_parts][P] fp64.  Per element: rows part_off[p] ..
+ * part_off[p + 1] - 1 added in that order in fp32 starting from the first row, one IEEE fp32
+ * division by (float)count, widened to double -- np.average along axis 0 of a float32 array, so out
+ * equals dvector.align_embeddings exactly.  An empty partition gives zeros; offsets are clamped
+ * into [0, S].  Any P >= 1; emb and out 16-byte aligned, part_off 4-byte (SV_EALIGN); null
+ * pointers or S, P, n_parts < 1 are SV_EARG.  No atomics, no workspace. */
+int sv_dvec_align(const float* emb, int S, int P, const int* part_off, int n_parts, double* out, hipStream_t stream);
+
 /* ---- clip_grad_norm_ + SGD step over one flat parameter group (train_speech_embedder.py:63-65)
  * p -= lr * min(1, max_norm / (|g|_2 + 1e-6)) * g; write_grad=1 also scales g in place.
  * sync (may be NULL): a persistent-recurrence sync block; if its status is set the step is

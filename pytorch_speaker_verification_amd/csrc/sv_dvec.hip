@@ -246,6 +246,39 @@ __global__ void dvec_x_kernel(const float* __restrict__ x, int B, int Bp, int T,
   const int b = (int)(tb % Bp), t = (int)(tb / Bp);
   xpad[i] = (b < B && k < F) ? to_bf(x[((long)b * T + t) * F + k]) : (bf16_t)0;
 }
+// dvec_x_kernel reading its windows in place: window b, step t is row win_start[b] + t of the
+// time-major frames [n_rows][F] fp32 (clamped into the table, so a bad win_start never reads
+// outside frames).  A thread converts 4 consecutive features of one (t, b): a 16-byte load where
+// the row pitch allows it (F % 4 == 0), an 8-byte store; the lanes of a wave cover 4 whole xpad
+// rows.  The same to_bf of the same values as dvec_x_kernel: the same bits.
+__global__ void dvec_frames_kernel(const float* __restrict__ frames, int n_rows, const int* __restrict__ win_start,
+                                   int B, int Bp, int T, int F, int Kx, bf16_t* __restrict__ xpad) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int kq = Kx / 4;
+  const long n = (long)T * Bp * kq;
+  if (i >= n) return;
+  const int k = 4 * (int)(i % kq);
+  const long tb = i / kq;
+  const int b = (int)(tb % Bp), t = (int)(tb / Bp);
+  bf16_t v[4] = {0, 0, 0, 0};
+  if (b < B && k < F) {
+    const long row = min(max((long)win_start[b] + t, 0L), (long)n_rows - 1);
+    const float* src = frames + row * F + k;
+    if (F % 4 == 0) {
+      const f32x4 x = *reinterpret_cast<const f32x4*>(src);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = to_bf(x[j]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (k + j < F) v[j] = to_bf(src[j]);
+    }
+  }
+  uint2 o;
+  o.x = (unsigned)v[0] | (unsigned)v[1] << 16;
+  o.y = (unsigned)v[2] | (unsigned)v[3] << 16;
+  *reinterpret_cast<uint2*>(xpad + 4 * i) = o;
+}
 size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
 }  // namespace
 
@@ -264,14 +297,18 @@ extern "C" size_t sv_dvector_bf16_workspace(int B, int T, int F, int H, int L, i
 // embeddings of B windows x [B][T][F] (fp32, batch-first; F <= 64, H % 64 == 0, 4H % 256 == 0):
 // layers[l] = (w_ih [4H][F_l], w_hh [4H][H], b_ih, b_hh) fp32; projection w_p [P][H], b_p [P];
 // emb [B][P] = normalize(h_{T-1} w_p^T + b_p).  workspace: sv_dvector_bf16_workspace bytes.
-extern "C" int sv_dvector_embed_bf16(int B, int T, int F, int H, int L, const float* x, const float* const* w_ih,
-                                     const float* const* w_hh, const float* const* b_ih, const float* const* b_hh,
-                                     const float* w_p, const float* b_p, int P, float* emb, void* workspace,
-                                     hipStream_t stream) {
-  if (B <= 0 || T <= 0 || L <= 0 || F <= 0 || F > DV_KX0 || H % G256_BK || (4 * H) % G256_BM || !x || !w_ih ||
-      !w_hh || !w_p || !emb || !workspace)
+// x != NULL: the windows themselves (dvec_x_kernel); else rows win_start[b] + t of frames
+// (dvec_frames_kernel).  Everything after the prep kernel is common.
+static int dvec_embed(int B, int T, int F, int H, int L, const float* x, const float* frames, int n_rows,
+                      const int* win_start, const float* const* w_ih, const float* const* w_hh,
+                      const float* const* b_ih, const float* const* b_hh, const float* w_p, const float* b_p, int P,
+                      float* emb, void* workspace, hipStream_t stream) {
+  if (B <= 0 || T <= 0 || L <= 0 || F <= 0 || F > DV_KX0 || H % G256_BK || (4 * H) % G256_BM || !w_ih || !w_hh ||
+      !w_p || !emb || !workspace)
     return SV_EARG;
+  if (!x && (!frames || !win_start || n_rows < 1)) return SV_EARG;
   if ((uintptr_t)workspace & 255) return SV_EALIGN;
+  if (!x && (((uintptr_t)frames & 15) || ((uintptr_t)win_start & 3))) return SV_EALIGN;
   const int Bp = (B + 255) / 256 * 256;
   char* ws = static_cast<char*>(workspace);
   bf16_t* xpad = reinterpret_cast<bf16_t*>(ws);
@@ -285,8 +322,12 @@ extern "C" int sv_dvector_embed_bf16(int B, int T, int F, int H, int L, const fl
   ws += align256((size_t)Bp * H * 4);
   float* hlast = reinterpret_cast<float*>(ws);
   ws += align256((size_t)Bp * H * 4);
-  hipLaunchKernelGGL(dvec_x_kernel, dim3((unsigned)(((long)T * Bp * DV_KX0 + 255) / 256)), dim3(256), 0, stream, x, B,
-                     Bp, T, F, DV_KX0, xpad);
+  if (x)
+    hipLaunchKernelGGL(dvec_x_kernel, dim3((unsigned)(((long)T * Bp * DV_KX0 + 255) / 256)), dim3(256), 0, stream, x, B,
+                       Bp, T, F, DV_KX0, xpad);
+  else
+    hipLaunchKernelGGL(dvec_frames_kernel, dim3((unsigned)(((long)T * Bp * (DV_KX0 / 4) + 255) / 256)), dim3(256), 0,
+                       stream, frames, n_rows, win_start, B, Bp, T, F, DV_KX0, xpad);
   SV_LAUNCH_CHECK();
   const size_t lds = G256_LDS;
   const int grid = (Bp / G256_BM) * (4 * H / G256_BM);
@@ -329,4 +370,24 @@ extern "C" int sv_dvector_embed_bf16(int B, int T, int F, int H, int L, const fl
   float* ynorm = reinterpret_cast<float*>(ws);
   ws += align256((size_t)B * 4);
   return sv_proj_norm_fwd(hlast, B, H, P, w_p, b_p, y, emb, ynorm, reinterpret_cast<float*>(ws), stream);
+}
+
+extern "C" int sv_dvector_embed_bf16(int B, int T, int F, int H, int L, const float* x, const float* const* w_ih,
+                                     const float* const* w_hh, const float* const* b_ih, const float* const* b_hh,
+                                     const float* w_p, const float* b_p, int P, float* emb, void* workspace,
+                                     hipStream_t stream) {
+  if (!x) return SV_EARG;
+  return dvec_embed(B, T, F, H, L, x, nullptr, 0, nullptr, w_ih, w_hh, b_ih, b_hh, w_p, b_p, P, emb, workspace, stream);
+}
+
+// sv_dvector_embed_bf16 with the windows read in place: window b, step t is row win_start[b] + t of
+// frames [n_rows][F] (time-major log-mel rows, sv_logmel's out); no [B][T][F] window tensor exists
+extern "C" int sv_dvector_embed_bf16_frames(int B, int T, int F, int H, int L, const float* frames, int n_rows,
+                                            const int* win_start, const float* const* w_ih,
+                                            const float* const* w_hh, const float* const* b_ih,
+                                            const float* const* b_hh, const float* w_p, const float* b_p, int P,
+                                            float* emb, void* workspace, hipStream_t stream) {
+  if (!frames || !win_start) return SV_EARG;
+  return dvec_embed(B, T, F, H, L, nullptr, frames, n_rows, win_start, w_ih, w_hh, b_ih, b_hh, w_p, b_p, P, emb,
+                    workspace, stream);
 }

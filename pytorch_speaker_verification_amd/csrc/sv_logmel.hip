@@ -27,6 +27,11 @@
 // the raw mel sums x of every valid frame row into seg_max[its segment] by an unsigned integer
 // atomic max on the float's bits (x >= 0: exact, and independent of the order of arrival).
 // meldb_clip_kernel then lifts every element to its own segment's maximum - top_db.
+// Range mode (sv_logmel_ranges of the C ABI, the third instantiation): the power epilogue on
+// segments given as (seg_start, seg_len) ranges of the one uploaded buffer -- they may touch, overlap
+// or leave gaps, so the voiced ranges of many files are framed without re-packing the audio.  A
+// frame row's origin, length and tap 0 are the only things read from the tables, so a range's frames
+// are bit-identical to sv_logmel's of a packed copy of it.
 #include "sv_common.h"
 #include "../../include/sv_ge2e.h"
 
@@ -44,10 +49,12 @@ constexpr int LM_MT = 4;                    // at most 4 mel tiles of 32 rows (n
 
 constexpr int LM_POWER = 0;  // |.|^2, log10(. + 1e-6); segments from seg_off (sv_logmel)
 constexpr int LM_MAGDB = 1;  // |.|, 20 log10(max(., amin)), per-segment maximum; virtual segments (sv_meldb)
+constexpr int LM_RANGES = 2;  // LM_POWER's epilogue; segments from seg_start and seg_len (sv_logmel_ranges)
 
 // NMT: mel tiles of 32 rows, (nmels + 31) / 32
-// MODE: LM_POWER (seg_off [n_seg + 1]; seg_valid, seg_len, amin, seg_max unused) or LM_MAGDB
-//       (seg_off is seg_start [n_seg])
+// MODE: LM_POWER (seg_off [n_seg + 1]; seg_valid, seg_len, amin, seg_max unused), LM_MAGDB
+//       (seg_off is seg_start [n_seg]) or LM_RANGES (seg_off is seg_start [n_seg], seg_len [n_seg];
+//       seg_valid, amin, seg_max unused)
 template <int NMT, int MODE>
 __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ y, const int* __restrict__ seg_off,
                                                      const int* __restrict__ frame_off, int n_seg, int n_frames,
@@ -86,6 +93,8 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ y
         n = seg_len[lo];
         nv = seg_valid[lo];
         sg = lo;
+      } else if constexpr (MODE == LM_RANGES) {
+        n = seg_len[lo];
       } else {
         n = seg_off[lo + 1] - y0;
       }
@@ -384,6 +393,36 @@ extern "C" int sv_logmel(const float* y, const int* seg_off, const int* frame_of
   hipLaunchKernelGGL((logmel_kernel<NMT, LM_POWER>), grid, dim3(256), 0, stream, y, seg_off, frame_off, n_seg, \
                      n_frames, nfft, win, hop, nmels, wbasis, ldw, melfb, out, (const int*)nullptr,          \
                      (const int*)nullptr, 0.f, (unsigned*)nullptr)
+  switch (nmt) {
+    case 1: LM_LAUNCH(1); break;
+    case 2: LM_LAUNCH(2); break;
+    case 3: LM_LAUNCH(3); break;
+    default: LM_LAUNCH(4); break;
+  }
+#undef LM_LAUNCH
+  SV_LAUNCH_CHECK();
+  return SV_OK;
+}
+
+extern "C" int sv_logmel_ranges(const float* y, const int* seg_start, const int* seg_len, const int* frame_off,
+                                int n_seg, int n_frames, int nfft, int win, int hop, int nmels, const float* wbasis,
+                                long ld_wbasis, const float* melfb, float* out, void* workspace, hipStream_t stream) {
+  (void)workspace;
+  if (!y || !seg_start || !seg_len || !frame_off || !wbasis || !melfb || !out || n_seg < 1 || n_frames < n_seg)
+    return SV_EARG;
+  if (nfft < 2 || nfft > 1024 || nfft % 2 || win < 1 || win > nfft || hop < 1 || nmels < 1 || nmels > 32 * LM_MT)
+    return SV_ESHAPE;
+  if (ld_wbasis < nfft + 2) return SV_EARG;
+  if (ld_wbasis % 4 || (((uintptr_t)y | (uintptr_t)wbasis | (uintptr_t)melfb | (uintptr_t)out) & 15) ||
+      (((uintptr_t)seg_start | (uintptr_t)seg_len | (uintptr_t)frame_off) & 3))
+    return SV_EALIGN;
+  if (ld_wbasis > (1L << 20)) return SV_EARG;  // (the kernel indexes the table with 32-bit offsets)
+  const int nmt = (nmels + 31) / 32, ldw = (int)ld_wbasis;
+  const dim3 grid((n_frames + LM_BM - 1) / LM_BM);
+#define LM_LAUNCH(NMT)                                                                                           \
+  hipLaunchKernelGGL((logmel_kernel<NMT, LM_RANGES>), grid, dim3(256), 0, stream, y, seg_start, frame_off, n_seg, \
+                     n_frames, nfft, win, hop, nmels, wbasis, ldw, melfb, out, (const int*)nullptr, seg_len, 0.f, \
+                     (unsigned*)nullptr)
   switch (nmt) {
     case 1: LM_LAUNCH(1); break;
     case 2: LM_LAUNCH(2); break;

@@ -3,17 +3,31 @@
 The reference turns each VAD-concatenated segment's log-mel spectrogram [nmels, T] into
 24-frame windows at a 12-frame hop (0.24 s / 0.12 s, :48-52), embeds all windows with the
 SpeechEmbedder (:100) and averages consecutive window embeddings into ~0.4 s segments
-(align_embeddings, :55-73).  Audio I/O and VAD (webrtcvad) stay out of scope; embed_segments
-starts from a file's waveform segments (features.logmel is the STFT / log-mel front end), the
-rest of the module from the log-mel frames.  The embedding is the short-sequence, large-batch
-forward of the same HIP LSTM kernels (T = 24).
+(align_embeddings, :55-73).  embed_segments starts from a file's waveform segments
+(features.logmel is the STFT / log-mel front end), the rest of the module from the log-mel frames.
+The embedding is the short-sequence, large-batch forward of the same HIP LSTM kernels (T = 24).
+
+The corpus export (dvector_create.py:84-122, the module-level loop that writes
+train_sequence.npy / train_cluster_id.npy / test_*.npy for uis-rnn) is export_sequences over
+embed_files: per batch of files one packed upload, one sv_logmel_ranges launch over the voiced
+ranges of all files, one window table, the embedding (bf16: sv_dvector_embed_bf16_frames, which
+reads its windows in place from the log-mel rows), one sv_dvec_align launch and one copy out.  Its
+input is what VAD_segments.VAD_chunk and concat_segs compute after the per-frame VAD decision:
+vad_frame_count / vad_times / voiced_ranges are that bookkeeping (frame_generator, vad_collector,
+the 0.4 s chunking, concat_segs) on per-frame is_speech flags from any VAD.  Only the per-frame
+decision itself (webrtcvad) and audio decoding stay outside.
 """
 from __future__ import annotations
+
+import collections
+import os
 
 import numpy as np
 import torch
 
-from .ops import check_persistent_status, embedder_forward, embedder_forward_bf16, embedder_forward_dvec_bf16
+from .hparam import hparam as hp
+from .ops import (check_persistent_status, dvec_align, embedder_forward, embedder_forward_bf16,
+                  embedder_forward_dvec_bf16, embedder_forward_dvec_bf16_frames)
 
 WIN, HOP = 24, 12  # frames: int(.24/.01), int(.12/.01)
 # bf16: from this many windows on, one pass of per-timestep GEMM launches with the cell in their
@@ -217,3 +231,245 @@ def embed_segments(net, segs, precision="f32", **kw):
         return np.zeros((0, proj))
     emb = embed_windows(net, windows, precision=precision, **kw)
     return align_embeddings(emb.cpu().numpy())
+
+
+# ---- the reference's VAD bookkeeping on per-frame flags (VAD_segments.py, dvector_create.concat_segs) ----
+def _sr(sr):
+    return hp.data.sr if sr is None else sr
+
+
+def vad_frame_count(n_samples, sr=None, frame_ms=20):
+    """How many frames VAD_segments.frame_generator yields for 16-bit PCM of n_samples samples: with
+    n = int(sr * (frame_ms / 1000.0) * 2) bytes per frame, frames run while offset + n < 2 * n_samples
+    (strict: a frame that would end exactly at the last byte is not yielded)."""
+    n = int(_sr(sr) * (frame_ms / 1000.0) * 2)
+    return max(0, (2 * int(n_samples) - 1) // n)
+
+
+def vad_times(is_speech, sr=None, frame_ms=20, padding_ms=200):
+    """VAD_chunk's speech_times from per-frame VAD decisions (one boolean per frame of
+    frame_generator, in order; any VAD may have made them): vad_collector's padded sliding window
+    (trigger when more than 0.9 maxlen of the ring's frames are voiced, detrigger when more than
+    0.9 maxlen are unvoiced, the leftover voiced span at the end of input) and then the chunking
+    of every span into 0.4 s pieces.  The reference's float arithmetic is kept literally -- frame
+    timestamps accumulate by repeated `+= duration`, spans and chunk ends are np.round(., 2), the
+    loop is `while j + .4 < end` with its else -- so the times compare equal (==) to the reference's,
+    which concat_segs relies on.  A list of (start, end) float pairs; no speech gives []."""
+    sr = _sr(sr)
+    n = int(sr * (frame_ms / 1000.0) * 2)
+    duration = (float(n) / sr) / 2.0
+    ring = collections.deque(maxlen=int(padding_ms / frame_ms))
+    triggered, voiced, start = False, False, 0.0
+    timestamp, end_of_last = 0.0, 0.0
+    spans = []
+    for speech in is_speech:
+        speech = bool(speech)
+        if not triggered:
+            ring.append((timestamp, speech))
+            if len([1 for _, s in ring if s]) > 0.9 * ring.maxlen:
+                triggered, voiced = True, True
+                start = ring[0][0]
+                ring.clear()
+        else:
+            voiced = True
+            ring.append((timestamp, speech))
+            if len([1 for _, s in ring if not s]) > 0.9 * ring.maxlen:
+                triggered, voiced = False, False
+                spans.append((start, timestamp + duration))
+                ring.clear()
+        end_of_last = timestamp + duration
+        timestamp += duration
+    if voiced:
+        spans.append((start, end_of_last))
+    times = []
+    for t0, t1 in spans:
+        start, end = np.round(t0, decimals=2), np.round(t1, decimals=2)
+        j = start
+        while j + .4 < end:
+            end_j = np.round(j + .4, decimals=2)
+            times.append((float(j), float(end_j)))
+            j = end_j
+        else:
+            times.append((float(j), float(end)))
+    return times
+
+
+def voiced_ranges(times, n_samples, sr=None):
+    """dvector_create.concat_segs as sample ranges [(a, b)] of the waveform: chunk i of VAD_chunk is
+    audio[int(t0 * sr):int(t1 * sr)], and consecutive chunks with times[i][1] == times[i + 1][0]
+    are concatenated.  Such chunks are contiguous in the waveform (the next starts at the very
+    int(t * sr) the last ended at), so every concatenated segment is one slice: (int(first t0 * sr),
+    int(last t1 * sr)), both clamped to n_samples as the slice clamps them.
+
+    Ranges with fewer than WIN + 1 log-mel frames (1 + (b - a) // hop <= WIN: shorter than 3840
+    samples at the default configuration) are dropped.  They give no window in get_STFTs (its
+    `j + 24 < T`), so nothing is lost, and every kept range is longer than the log-mel's minimum
+    of nfft // 2 + 1 samples."""
+    sr = _sr(sr)
+    hop_n = int(hp.data.hop * sr)
+    out = []
+    i = 0
+    while i < len(times):
+        k = i
+        while k + 1 < len(times) and times[k][1] == times[k + 1][0]:
+            k += 1
+        a, b = min(int(times[i][0] * sr), n_samples), min(int(times[k][1] * sr), n_samples)
+        b = max(a, b)
+        if 1 + (b - a) // hop_n > WIN:
+            out.append((a, b))
+        i = k + 1
+    return out
+
+
+def window_starts(frame_off, win=WIN, hop=HOP):
+    """(starts, counts): the int32 first-row table [S] of every window of every segment -- equal to
+    window_index(frame_off)[:, 0] -- and the number of windows of each segment."""
+    starts, counts = [], []
+    for a, b in zip(frame_off[:-1], frame_off[1:]):
+        s = np.arange(0, max(b - a - win, 0), hop, dtype=np.int64)  # j + win < T
+        starts.append(a + s)
+        counts.append(int(s.size))
+    starts = np.concatenate(starts) if starts else np.zeros(0, dtype=np.int64)
+    return starts.astype(np.int32), counts
+
+
+# ---- the corpus export (dvector_create.py:84-122) ----
+def batch_tables(frame_off, seg_file, n_files):
+    """The two device tables of one embed_files batch, from the log-mel frame offsets of its ranges
+    and the file index of every range: (win_start [S] int32, window_starts' table; part_off
+    [n_parts + 1] int32, every file's partitions() as row offsets into the batch's S embeddings;
+    the number of partitions of each file).  Every file must hold at least one window."""
+    starts, counts = window_starts(frame_off)
+    nwin = np.bincount(seg_file, weights=counts, minlength=n_files).astype(np.int64)
+    parts = [partitions(int(n)) for n in nwin]
+    base = np.concatenate([[0], np.cumsum(nwin)])
+    part_off = np.concatenate([[base[f] + a for a, _ in p] for f, p in enumerate(parts)] + [[base[-1]]])
+    return starts, part_off.astype(np.int32), [len(p) for p in parts]
+
+
+def _batches(sizes, max_samples):
+    """Consecutive index groups whose sizes add up to at most max_samples (a larger item alone)."""
+    groups, cur, tot = [], [], 0
+    for i, n in enumerate(sizes):
+        if cur and tot + n > max_samples:
+            groups.append(cur)
+            cur, tot = [], 0
+        cur.append(i)
+        tot += n
+    if cur:
+        groups.append(cur)
+    return groups
+
+
+@torch.no_grad()
+def embed_files(net, files, precision="bf16", path=None, max_samples=2 ** 27, **kw):
+    """Aligned d-vectors of many files: `files` is a list of (waveform, ranges), a decoded mono
+    waveform at hp.data.sr and its voiced sample ranges [(a, b)] (voiced_ranges); returns one
+    float64 [n_aligned_i, proj] array per file, in order -- per file what
+    embed_segments(net, [wave[a:b] for a, b in ranges]) gives.  A file with no range or no window
+    gives np.zeros((0, proj)); ranges too short for a window are not framed at all.
+
+    Files are grouped into batches of at most max_samples samples.  Per batch: one packed upload of
+    the waveforms and all tables, one sv_logmel_ranges launch over all ranges of all files, one
+    window_starts table, the embedding, one sv_dvec_align launch over every file's partitions()
+    and one copy out.  The embedding, in bf16 with dvec_ok(F, H) and (path == "dvec" or, with
+    path None, at least DVEC_MIN windows in the batch): sv_dvector_embed_bf16_frames in chunks of
+    DVEC_CHUNK windows, which reads the windows in place -- no window tensor exists.  Otherwise
+    (fp32, small bf16 batches, path == "persist"): the windows of one chunk at a time gathered on the
+    device from the same table (windows_from_logmel's gather) and embed_windows(**kw) on them, so
+    the window tensor stays bounded by the chunk (kw's `batch`, else embed_windows' default).
+    Raises PersistentRecurrenceError like embed_windows."""
+    from .features import _config, logmel_ranges
+    if precision not in ("f32", "bf16"):
+        raise ValueError(f"precision must be 'f32' or 'bf16', got {precision!r}")
+    if path not in (None, "persist", "dvec") or (path is not None and precision != "bf16"):
+        raise ValueError(f"path must be None, 'persist' or 'dvec' (bf16 only), got {path!r}")
+    _, _, _, hop_n, nmels = _config(None, None, None, None, None)
+    layers = net.LSTM_stack.layer_params()
+    wp, bp = net.projection.weight, net.projection.bias
+    proj, H = wp.shape[0], layers[0][1].shape[1]
+    if path == "dvec" and not dvec_ok(nmels, H):
+        raise ValueError(f"the per-timestep GEMM path needs F <= 64, H % 64 == 0 and 4H % 256 == 0 (F={nmels}, H={H})")
+    results = [np.zeros((0, proj)) for _ in files]
+    # only ranges that hold a window are framed (the others give nothing: get_STFTs' j + 24 < T)
+    kept = [[(int(a), int(b)) for a, b in ranges if 1 + (int(b) - int(a)) // hop_n > WIN] for _, ranges in files]
+    live = [i for i, r in enumerate(kept) if r]
+    for group in _batches([int(files[i][0].shape[0]) for i in live], max_samples):
+        ids = [live[g] for g in group]
+        ranges = [(w, a, b) for w, i in enumerate(ids) for a, b in kept[i]]
+        seg_file = [w for w, i in enumerate(ids) for _ in kept[i]]
+        n_parts = []
+
+        def tables(frame_off):  # (every file of the batch has a range with a window)
+            starts, part_off, n_parts[:] = batch_tables(frame_off, seg_file, len(ids))
+            return [starts, part_off]
+
+        out, _, (win_start, part_off) = logmel_ranges([files[i][0] for i in ids], ranges, tables=tables)
+        S = int(win_start.shape[0])
+        with torch.cuda.device(out.device):
+            if precision == "bf16" and dvec_ok(nmels, H) and (path == "dvec" or (path is None and S >= DVEC_MIN)):
+                emb = [embedder_forward_dvec_bf16_frames(out, win_start[i:i + DVEC_CHUNK], layers, wp, bp)
+                       for i in range(0, S, DVEC_CHUNK)]
+                check_persistent_status(wait=True)
+            else:
+                chunk = kw.get("batch") or (bf16_batch(H) if precision == "bf16" else 16384)
+                steps = torch.arange(WIN, device=out.device)
+                emb = [embed_windows(net, out[win_start[i:i + chunk].long()[:, None] + steps[None, :]], precision=precision,
+                                     path=path, **kw) for i in range(0, S, chunk)]
+            emb = emb[0] if len(emb) == 1 else torch.cat(emb)
+            aligned = dvec_align(emb, part_off).cpu().numpy()
+        pos = 0
+        for i, n in zip(ids, n_parts):
+            results[i] = aligned[pos:pos + n]
+            pos += n
+    return results
+
+
+def export_sequences(net, speakers, out_dir, **kw):
+    """The module-level loop of dvector_create.py:84-122 on decoded audio: `speakers` is a list
+    (one entry per folder) of lists of (waveform, ranges) files (ranges from voiced_ranges).  Writes
+    train_sequence.npy, train_cluster_id.npy, test_sequence.npy and test_cluster_id.npy into
+    out_dir and returns the four arrays (train sequence, train ids, test sequence, test ids):
+    sequences float64 [n, proj], the files' aligned d-vectors concatenated in order; ids np.asarray
+    of one label string per row.
+
+    As in the reference, the label is the folder's index as str and counts every folder, also one
+    without a usable file; a file without voiced audio (no ranges: the reference's `segs == []`) is
+    skipped.  A file whose ranges hold no window, where the reference would crash in np.stack([]),
+    is skipped too.  The train part is closed after the first folder with index
+    i > (len(speakers) // 10) * 9 -- so it holds folders 0 .. (len // 10) * 9 + 1 -- and the rest is
+    the test part.  Where the reference's np.concatenate([]) would raise -- a part without a single
+    d-vector, or no folder at all past the train part -- ValueError names the part and nothing is
+    written; so does a corpus too small for the train part ever to be closed (fewer than two
+    folders), where the reference would write the test files alone.
+
+    All folders go through one embed_files call (**kw); the split is applied afterwards."""
+    total = len(speakers)
+    train_speaker_num = (total // 10) * 9
+    flat = [f for folder in speakers for f in folder]
+    embedded = iter(embed_files(net, flat, **kw))
+    parts = {"train": ([], []), "test": ([], [])}
+    train_saved = False
+    for i, folder in enumerate(speakers):
+        seq, ids = parts["test" if train_saved else "train"]
+        for _ in folder:
+            aligned = next(embedded)
+            if len(aligned) == 0:
+                continue  # no voice activity detected (or no window in what was detected)
+            seq.append(aligned)
+            ids.extend([str(i)] * len(aligned))
+        if not train_saved and i > train_speaker_num:
+            train_saved = True
+    if not train_saved:
+        raise ValueError(f"the train part is never closed with {total} folder(s): nothing written")
+    for name, (seq, _) in parts.items():
+        if not seq:
+            raise ValueError(f"the {name} part holds no d-vector: nothing written")
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = []
+    for name, (seq, ids) in parts.items():
+        sequence, cluster_id = np.concatenate(seq, axis=0), np.asarray(ids)
+        np.save(os.path.join(out_dir, f"{name}_sequence.npy"), sequence)
+        np.save(os.path.join(out_dir, f"{name}_cluster_id.npy"), cluster_id)
+        arrays += [sequence, cluster_id]
+    return tuple(arrays)

@@ -25,7 +25,13 @@ amin 1e-5, top_db 80 against each utterance's own maximum), time-major, from the
 index arithmetic on the one uploaded buffer: a batch of utterances to ``[n, T, nmels]`` in one
 ``sv_frame_energy`` launch and one ``sv_meldb`` call.
 
-Audio decoding, resampling and VAD (webrtcvad) stay out of scope: this module starts from mono
+``logmel_ranges`` is ``logmel`` of ranges of one uploaded buffer (``sv_logmel_ranges``): the voiced
+ranges of many files, which may touch, overlap or leave gaps, are framed in one launch without
+re-packing the audio, each bit-identical to ``logmel`` of its slice.  It is the front of the corpus
+d-vector export (``dvector.embed_files``).
+
+Audio decoding, resampling and the per-frame VAD decision (webrtcvad) stay out of scope (the
+bookkeeping around that decision is ``dvector.vad_times`` / ``voiced_ranges``): this module starts from mono
 fp32 samples at ``hp.data.sr``.  So do the other two outputs of ``utils.mfccs_and_spec``:
 ``mag_db`` (the reference's dataset drops it) and ``calc_mfccs`` (a DCT over the time axis of the
 already transposed array, with ``librosa.filters.dct``, which librosa removed).
@@ -177,6 +183,81 @@ def logmel_into(y, seg_off, frame_off, n_seg, n_frames, nfft, win, hop, nmels, w
     """sv_logmel on device tensors (y fp32, offsets int32, out [>= n_frames, nmels] fp32 contiguous)."""
     _lib.call("sv_logmel", _lib.ptr(y), _lib.ptr(seg_off), _lib.ptr(frame_off), n_seg, n_frames, nfft, win, hop,
               nmels, _lib.ptr(wbasis), wbasis.stride(0), _lib.ptr(melfb), _lib.ptr(out), None, _lib.stream_of(out))
+
+
+def range_tables(lengths, ranges, nfft, hop):
+    """(seg_start, seg_len, frame_off) int32 arrays (n, n, n + 1) of sv_logmel_ranges for waveforms
+    of `lengths` samples packed back to back and `ranges` = (wave_index, a, b) entries, range r
+    being samples [a, b) of its waveform with 1 + (b - a) // hop frames.  ValueError for no range, a
+    wave index or bounds outside the waveform, a range shorter than nfft//2 + 1 samples (its reflect
+    padding would need a second reflection) and for totals past 32-bit offsets."""
+    lengths = np.asarray(lengths, dtype=np.int64)
+    r = np.asarray([(int(w), int(a), int(b)) for w, a, b in ranges], dtype=np.int64).reshape(-1, 3)
+    if r.shape[0] == 0:
+        raise ValueError("logmel_ranges needs at least one range")
+    bad = np.nonzero((r[:, 0] < 0) | (r[:, 0] >= lengths.size))[0]
+    if bad.size:
+        raise ValueError(f"range {int(bad[0])} names waveform {int(r[bad[0], 0])} of {lengths.size}")
+    n = lengths[r[:, 0]]
+    bad = np.nonzero((r[:, 1] < 0) | (r[:, 2] > n) | (r[:, 1] > r[:, 2]))[0]
+    if bad.size:
+        k = int(bad[0])
+        raise ValueError(f"range {k} [{int(r[k, 1])}, {int(r[k, 2])}) lies outside its waveform of {int(n[k])} samples")
+    seg_len = r[:, 2] - r[:, 1]
+    short = np.nonzero(seg_len < nfft // 2 + 1)[0]
+    if short.size:
+        raise ValueError(f"range {int(short[0])} has {int(seg_len[short[0]])} samples; reflect padding of an "
+                         f"nfft={nfft} STFT needs at least {nfft // 2 + 1}")
+    seg_off = np.concatenate([[0], np.cumsum(lengths)])
+    frame_off = np.concatenate([[0], np.cumsum(1 + seg_len // hop)])
+    if seg_off[-1] >= 2 ** 31 or frame_off[-1] * 128 >= 2 ** 31:
+        raise ValueError("too many samples for one logmel_ranges call (32-bit offsets): split the batch")
+    return (seg_off[r[:, 0]] + r[:, 1]).astype(np.int32), seg_len.astype(np.int32), frame_off.astype(np.int32)
+
+
+def logmel_ranges(y, ranges, sr=None, nfft=None, window=None, hop=None, nmels=None, tables=None):
+    """Log-mel frames of ranges of one waveform `y` (or of a list of waveforms, packed once; 1-D
+    arrays or tensors, host or device, mono at `sr`): `ranges` holds (wave_index, a, b) entries,
+    range r being samples [a, b) of waveform wave_index.  Returns (out [n_frames, nmels] cuda float32,
+    frame_off) with range r in rows frame_off[r] : frame_off[r + 1], each bit-identical to
+    logmel(wave[a:b]).  Ranges may touch, overlap or leave gaps: the audio is uploaded once and never
+    re-packed, one sv_logmel_ranges launch frames all of them.  ValueError (before any upload) for an
+    empty list, a range out of bounds or shorter than nfft//2 + 1 samples, and for totals past 32-bit
+    offsets.  `tables` (a callable frame_off -> list of int32 arrays) rides in the same upload; with
+    it the result is (out, frame_off, [the arrays on the device]) -- dvector.embed_files sends its
+    window and partition tables this way."""
+    sr, nfft, win, hop_n, nmels = _config(sr, nfft, window, hop, nmels)
+    waves = _as_list(y)
+    for s in waves:
+        if getattr(s, "ndim", None) != 1:
+            raise ValueError("each waveform must be a 1-D array or tensor of samples")
+    lengths = [int(s.shape[0]) for s in waves]
+    seg_start, seg_len, frame_off = range_tables(lengths, ranges, nfft, hop_n)
+    frame_off_l = [int(v) for v in frame_off]
+    extra = [np.ascontiguousarray(t, dtype=np.int32) for t in tables(frame_off_l)] if tables is not None else []
+    n_seg, n_frames = len(seg_len), frame_off_l[-1]
+    seg_off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+    y_dev, _, tab, dev = _pack(waves, seg_off, np.concatenate([seg_start, seg_len, frame_off] + extra))
+    wbasis, melfb = stft_tables(sr, nfft, win, nmels, dev)
+    out = torch.empty((n_frames, nmels), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        logmel_ranges_into(y_dev, tab[:n_seg], tab[n_seg:2 * n_seg], tab[2 * n_seg:3 * n_seg + 1], n_seg, n_frames, nfft,
+                           win, hop_n, nmels, wbasis, melfb, out)
+    if tables is None:
+        return out, frame_off_l
+    pos, on_dev = 3 * n_seg + 1, []
+    for t in extra:
+        on_dev.append(tab[pos:pos + t.size])
+        pos += t.size
+    return out, frame_off_l, on_dev
+
+
+def logmel_ranges_into(y, seg_start, seg_len, frame_off, n_seg, n_frames, nfft, win, hop, nmels, wbasis, melfb, out):
+    """sv_logmel_ranges on device tensors (y fp32; seg_start, seg_len [n_seg] and frame_off
+    [n_seg + 1] int32; out [>= n_frames, nmels] fp32 contiguous)."""
+    _lib.call("sv_logmel_ranges", _lib.ptr(y), _lib.ptr(seg_start), _lib.ptr(seg_len), _lib.ptr(frame_off), n_seg,
+              n_frames, nfft, win, hop, nmels, _lib.ptr(wbasis), wbasis.stride(0), _lib.ptr(melfb), _lib.ptr(out), None,
+              _lib.stream_of(out))
 
 
 def preprocess_utterance(utter, intervals, tisv_frame=None):

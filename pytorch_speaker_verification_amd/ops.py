@@ -427,6 +427,45 @@ def embedder_forward_dvec_bf16(x, layers, w_p, b_p):
     return emb
 
 
+def embedder_forward_dvec_bf16_frames(frames, win_start, layers, w_p, b_p):
+    """embedder_forward_dvec_bf16 with the windows read in place (sv_dvector_embed_bf16_frames):
+    frames [n_rows, F] fp32 are time-major log-mel rows (features.logmel's out), win_start [B]
+    int32 on the same device the first row of every window; window b, step t is row
+    win_start[b] + t (T = dvector.WIN rows, clamped into frames).  No [B, T, F] window tensor is
+    built; the embeddings [B, P] are bit-identical to embedder_forward_dvec_bf16 on the
+    materialised windows at the same B."""
+    from .dvector import WIN
+    require_device(frames, w_p, *[t for l in layers for t in l if t is not None])
+    if not win_start.is_cuda or win_start.dtype != torch.int32 or not win_start.is_contiguous() or win_start.dim() != 1:
+        raise RuntimeError("win_start must be a contiguous 1-D int32 tensor on the GPU")
+    n_rows, F = frames.shape
+    B, T = win_start.shape[0], WIN
+    H = layers[0][1].shape[1]
+    P = w_p.shape[0]
+    L = len(layers)
+    emb = torch.empty((B, P), dtype=torch.float32, device=frames.device)
+    ws = _ws(lib().sv_dvector_bf16_workspace(B, T, F, H, L, P), frames.device)
+    ts = [[l[i].contiguous() if l[i] is not None else None for l in layers] for i in range(4)]  # kept alive
+    wih, whh, bih, bhh = (_parr(t) for t in ts)
+    call("sv_dvector_embed_bf16_frames", B, T, F, H, L, ptr(frames), n_rows, ptr(win_start), wih, whh, bih, bhh,
+         ptr(w_p.contiguous()), ptr(b_p) if b_p is not None else None, P, ptr(emb), ptr(ws), stream_of(frames))
+    return emb
+
+
+def dvec_align(emb, part_off):
+    """Rows part_off[p] : part_off[p + 1] of emb [S, P] (fp32) averaged into out [n_parts, P]
+    float64 on the device (sv_dvec_align; part_off a device int32 tensor of n_parts + 1 offsets):
+    equal to np.average of each float32 row block, i.e. to dvector.align_embeddings, exactly."""
+    require_device(emb)
+    if not part_off.is_cuda or part_off.dtype != torch.int32 or not part_off.is_contiguous() or part_off.dim() != 1:
+        raise RuntimeError("part_off must be a contiguous 1-D int32 tensor on the GPU")
+    S, P = emb.shape
+    n_parts = part_off.shape[0] - 1
+    out = torch.empty((n_parts, P), dtype=torch.float64, device=emb.device)
+    call("sv_dvec_align", ptr(emb), S, P, ptr(part_off), n_parts, ptr(out), stream_of(emb))
+    return out
+
+
 def embedder_backward_bf16(st, demb, layers, w_p, grads=None, grad_ready=None, status=None, probe=None,
                            schedule="auto", need_dx=False):
     """Backward of embedder_forward_bf16 (same ``grads`` / ``grad_ready`` contract as
