@@ -143,6 +143,27 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return v;
 }
 
+// The waveform front end's two index rules (sv_logmel.hip, sv_split.hip), templated on the index
+// type so that each kernel keeps its own width (int there, long here).
+// The last segment whose first frame is <= g: a bisection of frame_off [n_seg + 1]
+template <typename I>
+__device__ __forceinline__ int seg_of_frame(const int* __restrict__ frame_off, int n_seg, I g) {
+  int lo = 0, hi = n_seg - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (frame_off[mid] <= g) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+// Index i of a signal of n samples under reflect padding: reflected once at each end, then clamped
+// into [0, n) (a signal too short for one reflection stays inside itself)
+template <typename I>
+__device__ __forceinline__ I reflect_clamp(I i, int n) {
+  i = i < 0 ? -i : i;
+  i = i >= n ? 2 * ((I)n - 1) - i : i;
+  return min(max(i, (I)0), (I)n - 1);
+}
+
 // f32 -> bf16 bits, round-to-nearest-even (inputs are finite activations/weights)
 __device__ __forceinline__ unsigned short f2bf(float f) {
   unsigned u = __float_as_uint(f);

@@ -78,27 +78,20 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ y
   const int g0 = blockIdx.x * LM_BM;
   const int nh = nfft / 2, nb = nh + 1, lpad = (nfft - win) / 2;
 
+  // segment s under the MODE: its origin in y, its length and (MAG) its count of real samples
+  auto segment = [&](int s, int& y0, int& n, int& nv) {
+    y0 = seg_off[s];
+    n = MODE == LM_POWER ? seg_off[s + 1] - y0 : seg_len[s];
+    if constexpr (MAG) nv = seg_valid[s];
+  };
   if (tid < LM_BM) {
     const int g = g0 + tid;
     int y0 = 0, n = 1, base = 0;  // rows past n_frames read y[0]; their columns are never stored
     int nv = 0, sg = 0;
     if (g < n_frames) {
-      int lo = 0, hi = n_seg - 1;  // the last segment whose first frame is <= g
-      while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (frame_off[mid] <= g) lo = mid; else hi = mid - 1;
-      }
-      y0 = seg_off[lo];
-      if constexpr (MAG) {
-        n = seg_len[lo];
-        nv = seg_valid[lo];
-        sg = lo;
-      } else if constexpr (MODE == LM_RANGES) {
-        n = seg_len[lo];
-      } else {
-        n = seg_off[lo + 1] - y0;
-      }
-      base = (g - frame_off[lo]) * hop + lpad - nh;  // sample index of tap 0 before reflection
+      sg = seg_of_frame(frame_off, n_seg, g);
+      segment(sg, y0, n, nv);
+      base = (g - frame_off[sg]) * hop + lpad - nh;  // sample index of tap 0 before reflection
     }
     rows[tid] = y0;
     rows[LM_BM + tid] = n;
@@ -131,10 +124,7 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ y
     if constexpr (MAG) fz = 0u;
 #pragma unroll
     for (int i = 0; i < LM_FT; ++i) {
-      int idx = rbase[i] + tap;
-      idx = idx < 0 ? -idx : idx;
-      idx = idx >= rn[i] ? 2 * (rn[i] - 1) - idx : idx;
-      idx = min(max(idx, 0), rn[i] - 1);  // (a segment shorter than nfft / 2 + 1 stays inside itself)
+      int idx = reflect_clamp(rbase[i] + tap, rn[i]);
       if constexpr (MAG) {
         fz |= idx >= rv[i] ? 1u << i : 0u;
         idx = min(idx, max(rv[i], 1) - 1);
@@ -352,20 +342,47 @@ __global__ __launch_bounds__(256) void meldb_clip_kernel(const int* __restrict__
   if (tid < LM_BM) {
     const int g = g0 + tid;
     float lv = 0.f;
-    if (g < n_frames) {
-      int lo = 0, hi = n_seg - 1;  // the last segment whose first frame is <= g
-      while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (frame_off[mid] <= g) lo = mid; else hi = mid - 1;
-      }
-      lv = 20.f * log10f(fmaxf(seg_max[lo], amin)) - top_db;
-    }
+    if (g < n_frames) lv = 20.f * log10f(fmaxf(seg_max[seg_of_frame(frame_off, n_seg, g)], amin)) - top_db;
     level[tid] = lv;
   }
   __syncthreads();
   const int nvalid = min(LM_BM, n_frames - g0) * nmels;
   float* dst = out + (long)g0 * nmels;
   for (int i = tid; i < nvalid; i += 256) dst[i] = fmaxf(dst[i], level[i / nmels]);
+}
+
+// The argument checks the three entry points share, in their order: the configuration, the basis
+// table's row stride, alignment (tabs: the addresses of the entry point's 4-byte tables, or-ed
+// together) and the stride's limit.
+int lm_check(int nfft, int win, int hop, int nmels, long ld_wbasis, const float* y, const float* wbasis,
+             const float* melfb, const float* out, uintptr_t tabs) {
+  if (nfft < 2 || nfft > 1024 || nfft % 2 || win < 1 || win > nfft || hop < 1 || nmels < 1 || nmels > 32 * LM_MT)
+    return SV_ESHAPE;
+  if (ld_wbasis < nfft + 2) return SV_EARG;
+  if (ld_wbasis % 4 || (((uintptr_t)y | (uintptr_t)wbasis | (uintptr_t)melfb | (uintptr_t)out) & 15) || (tabs & 3))
+    return SV_EALIGN;
+  if (ld_wbasis > (1L << 20)) return SV_EARG;  // (the kernel indexes the table with 32-bit offsets)
+  return SV_OK;
+}
+
+// logmel_kernel<(nmels + 31) / 32, MODE> on 64 frames per workgroup
+template <int MODE>
+int lm_launch(hipStream_t stream, const float* y, const int* seg_off, const int* frame_off, int n_seg, int n_frames,
+              int nfft, int win, int hop, int nmels, const float* wbasis, long ld_wbasis, const float* melfb,
+              float* out, const int* seg_valid, const int* seg_len, float amin, unsigned* seg_max) {
+  const dim3 grid((n_frames + LM_BM - 1) / LM_BM);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, y, seg_off, frame_off, n_seg, n_frames, nfft, win, hop,
+                       nmels, wbasis, (int)ld_wbasis, melfb, out, seg_valid, seg_len, amin, seg_max);
+  };
+  switch ((nmels + 31) / 32) {
+    case 1: launch(logmel_kernel<1, MODE>); break;
+    case 2: launch(logmel_kernel<2, MODE>); break;
+    case 3: launch(logmel_kernel<3, MODE>); break;
+    default: launch(logmel_kernel<4, MODE>); break;
+  }
+  SV_LAUNCH_CHECK();
+  return SV_OK;
 }
 
 }  // namespace
@@ -380,28 +397,11 @@ extern "C" int sv_logmel(const float* y, const int* seg_off, const int* frame_of
                          float* out, void* workspace, hipStream_t stream) {
   (void)workspace;
   if (!y || !seg_off || !frame_off || !wbasis || !melfb || !out || n_seg < 1 || n_frames < n_seg) return SV_EARG;
-  if (nfft < 2 || nfft > 1024 || nfft % 2 || win < 1 || win > nfft || hop < 1 || nmels < 1 || nmels > 32 * LM_MT)
-    return SV_ESHAPE;
-  if (ld_wbasis < nfft + 2) return SV_EARG;
-  if (ld_wbasis % 4 || (((uintptr_t)y | (uintptr_t)wbasis | (uintptr_t)melfb | (uintptr_t)out) & 15) ||
-      (((uintptr_t)seg_off | (uintptr_t)frame_off) & 3))
-    return SV_EALIGN;
-  if (ld_wbasis > (1L << 20)) return SV_EARG;  // (the kernel indexes the table with 32-bit offsets)
-  const int nmt = (nmels + 31) / 32, ldw = (int)ld_wbasis;
-  const dim3 grid((n_frames + LM_BM - 1) / LM_BM);
-#define LM_LAUNCH(NMT)                                                                                       \
-  hipLaunchKernelGGL((logmel_kernel<NMT, LM_POWER>), grid, dim3(256), 0, stream, y, seg_off, frame_off, n_seg, \
-                     n_frames, nfft, win, hop, nmels, wbasis, ldw, melfb, out, (const int*)nullptr,          \
-                     (const int*)nullptr, 0.f, (unsigned*)nullptr)
-  switch (nmt) {
-    case 1: LM_LAUNCH(1); break;
-    case 2: LM_LAUNCH(2); break;
-    case 3: LM_LAUNCH(3); break;
-    default: LM_LAUNCH(4); break;
-  }
-#undef LM_LAUNCH
-  SV_LAUNCH_CHECK();
-  return SV_OK;
+  const int rc = lm_check(nfft, win, hop, nmels, ld_wbasis, y, wbasis, melfb, out,
+                          (uintptr_t)seg_off | (uintptr_t)frame_off);
+  if (rc) return rc;
+  return lm_launch<LM_POWER>(stream, y, seg_off, frame_off, n_seg, n_frames, nfft, win, hop, nmels, wbasis, ld_wbasis,
+                             melfb, out, nullptr, nullptr, 0.f, nullptr);
 }
 
 extern "C" int sv_logmel_ranges(const float* y, const int* seg_start, const int* seg_len, const int* frame_off,
@@ -410,28 +410,11 @@ extern "C" int sv_logmel_ranges(const float* y, const int* seg_start, const int*
   (void)workspace;
   if (!y || !seg_start || !seg_len || !frame_off || !wbasis || !melfb || !out || n_seg < 1 || n_frames < n_seg)
     return SV_EARG;
-  if (nfft < 2 || nfft > 1024 || nfft % 2 || win < 1 || win > nfft || hop < 1 || nmels < 1 || nmels > 32 * LM_MT)
-    return SV_ESHAPE;
-  if (ld_wbasis < nfft + 2) return SV_EARG;
-  if (ld_wbasis % 4 || (((uintptr_t)y | (uintptr_t)wbasis | (uintptr_t)melfb | (uintptr_t)out) & 15) ||
-      (((uintptr_t)seg_start | (uintptr_t)seg_len | (uintptr_t)frame_off) & 3))
-    return SV_EALIGN;
-  if (ld_wbasis > (1L << 20)) return SV_EARG;  // (the kernel indexes the table with 32-bit offsets)
-  const int nmt = (nmels + 31) / 32, ldw = (int)ld_wbasis;
-  const dim3 grid((n_frames + LM_BM - 1) / LM_BM);
-#define LM_LAUNCH(NMT)                                                                                           \
-  hipLaunchKernelGGL((logmel_kernel<NMT, LM_RANGES>), grid, dim3(256), 0, stream, y, seg_start, frame_off, n_seg, \
-                     n_frames, nfft, win, hop, nmels, wbasis, ldw, melfb, out, (const int*)nullptr, seg_len, 0.f, \
-                     (unsigned*)nullptr)
-  switch (nmt) {
-    case 1: LM_LAUNCH(1); break;
-    case 2: LM_LAUNCH(2); break;
-    case 3: LM_LAUNCH(3); break;
-    default: LM_LAUNCH(4); break;
-  }
-#undef LM_LAUNCH
-  SV_LAUNCH_CHECK();
-  return SV_OK;
+  const int rc = lm_check(nfft, win, hop, nmels, ld_wbasis, y, wbasis, melfb, out,
+                          (uintptr_t)seg_start | (uintptr_t)seg_len | (uintptr_t)frame_off);
+  if (rc) return rc;
+  return lm_launch<LM_RANGES>(stream, y, seg_start, frame_off, n_seg, n_frames, nfft, win, hop, nmels, wbasis,
+                              ld_wbasis, melfb, out, nullptr, seg_len, 0.f, nullptr);
 }
 
 extern "C" size_t sv_meldb_workspace(int n_frames, int nfft, int win, int nmels) {
@@ -447,33 +430,18 @@ extern "C" int sv_meldb(const float* y, const int* seg_start, const int* seg_val
   if (!y || !seg_start || !seg_valid || !seg_len || !frame_off || !wbasis || !melfb || !out || !seg_max || n_seg < 1 ||
       n_frames < n_seg || !(amin > 0.f))
     return SV_EARG;
-  if (nfft < 2 || nfft > 1024 || nfft % 2 || win < 1 || win > nfft || hop < 1 || nmels < 1 || nmels > 32 * LM_MT)
-    return SV_ESHAPE;
-  if (ld_wbasis < nfft + 2) return SV_EARG;
-  if (ld_wbasis % 4 || (((uintptr_t)y | (uintptr_t)wbasis | (uintptr_t)melfb | (uintptr_t)out) & 15) ||
-      (((uintptr_t)seg_start | (uintptr_t)seg_valid | (uintptr_t)seg_len | (uintptr_t)frame_off | (uintptr_t)seg_max) &
-       3))
-    return SV_EALIGN;
-  if (ld_wbasis > (1L << 20)) return SV_EARG;  // (the kernel indexes the table with 32-bit offsets)
-  const int nmt = (nmels + 31) / 32, ldw = (int)ld_wbasis;
-  const dim3 grid((n_frames + LM_BM - 1) / LM_BM);
-  const int rc = sv_zero_bytes(seg_max, (size_t)n_seg * sizeof(float), stream);
+  int rc = lm_check(nfft, win, hop, nmels, ld_wbasis, y, wbasis, melfb, out,
+                    (uintptr_t)seg_start | (uintptr_t)seg_valid | (uintptr_t)seg_len | (uintptr_t)frame_off |
+                        (uintptr_t)seg_max);
   if (rc) return rc;
-  unsigned* smax = reinterpret_cast<unsigned*>(seg_max);
-#define LM_LAUNCH(NMT)                                                                                         \
-  hipLaunchKernelGGL((logmel_kernel<NMT, LM_MAGDB>), grid, dim3(256), 0, stream, y, seg_start, frame_off, n_seg, \
-                     n_frames, nfft, win, hop, nmels, wbasis, ldw, melfb, out, seg_valid, seg_len, amin, smax)
-  switch (nmt) {
-    case 1: LM_LAUNCH(1); break;
-    case 2: LM_LAUNCH(2); break;
-    case 3: LM_LAUNCH(3); break;
-    default: LM_LAUNCH(4); break;
-  }
-#undef LM_LAUNCH
-  SV_LAUNCH_CHECK();
+  rc = sv_zero_bytes(seg_max, (size_t)n_seg * sizeof(float), stream);
+  if (rc) return rc;
+  rc = lm_launch<LM_MAGDB>(stream, y, seg_start, frame_off, n_seg, n_frames, nfft, win, hop, nmels, wbasis, ld_wbasis,
+                           melfb, out, seg_valid, seg_len, amin, reinterpret_cast<unsigned*>(seg_max));
+  if (rc) return rc;
   if (top_db >= 0.f) {
-    hipLaunchKernelGGL(meldb_clip_kernel, grid, dim3(256), 0, stream, frame_off, n_seg, n_frames, nmels,
-                       (const float*)seg_max, amin, top_db, out);
+    hipLaunchKernelGGL(meldb_clip_kernel, dim3((n_frames + LM_BM - 1) / LM_BM), dim3(256), 0, stream, frame_off, n_seg,
+                       n_frames, nmels, (const float*)seg_max, amin, top_db, out);
     SV_LAUNCH_CHECK();
   }
   return SV_OK;

@@ -32,11 +32,7 @@ __global__ __launch_bounds__(64 * FE_WAVES) void frame_energy_kernel(const float
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const long g = (long)blockIdx.x * FE_WAVES + w;
   if (g >= n_frames) return;
-  int lo = 0, hi = n_seg - 1;  // the last segment whose first frame is <= g
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (frame_off[mid] <= g) lo = mid; else hi = mid - 1;
-  }
+  const int lo = seg_of_frame(frame_off, n_seg, g);
   const int y0 = seg_off[lo], n = seg_off[lo + 1] - y0;
   if (n < 1) {  // an empty segment's one frame: nothing to read
     if (lane == 0) mse[g] = 0.f;
@@ -66,11 +62,7 @@ __global__ __launch_bounds__(64 * FE_WAVES) void frame_energy_kernel(const float
 #pragma unroll
       for (int k = 0; k < FE_ACC; ++k) {
         const int j = j0 + 64 * k + lane;
-        long i = base + j;
-        i = i < 0 ? -i : i;
-        i = i >= n ? 2 * ((long)n - 1) - i : i;
-        i = min(max(i, 0L), (long)n - 1);  // (a segment shorter than frame_length / 2 + 1 stays inside itself)
-        v[k] = ys[i];
+        v[k] = ys[reflect_clamp(base + j, n)];
         v[k] = j < fl ? v[k] : 0.f;
       }
 #pragma unroll

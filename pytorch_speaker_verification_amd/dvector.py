@@ -48,10 +48,9 @@ def window_frames(logmel, win=WIN, hop=HOP):
 
 def window_index(frame_off, win=WIN, hop=HOP):
     """Row indices [S, win] into time-major log-mel frames [n_frames, nmels] (features.logmel) of
-    every segment's windows: per segment of T_s frames, starts j = 0, hop, ... while j + win < T_s
-    (window_frames' rule, dvector_create.py:49), segments in order."""
-    starts = [a + j for a, b in zip(frame_off[:-1], frame_off[1:]) for j in range(0, b - a, hop) if j + win < b - a]
-    return np.asarray(starts, dtype=np.int64).reshape(-1, 1) + np.arange(win, dtype=np.int64)[None, :]
+    every segment's windows (window_starts' rows, dvector_create.py:49), segments in order."""
+    starts, _ = window_starts(frame_off, win, hop)
+    return starts.astype(np.int64)[:, None] + np.arange(win, dtype=np.int64)[None, :]
 
 
 def windows_from_logmel(out, frame_off, win=WIN, hop=HOP):
@@ -81,6 +80,19 @@ def bf16_batch(H, limit=16384):
     return b if lib().sv_persist_fwd_ok(b, H) else limit
 
 
+def _check_path(precision, path):
+    if precision not in ("f32", "bf16"):
+        raise ValueError(f"precision must be 'f32' or 'bf16', got {precision!r}")
+    if path not in (None, "persist", "dvec") or (path is not None and precision != "bf16"):
+        raise ValueError(f"path must be None, 'persist' or 'dvec' (bf16 only), got {path!r}")
+
+
+def _takes_dvec(precision, path, n_windows, F, H):
+    """Whether a bf16 embedding of n_windows windows takes the per-timestep GEMM path: asked for by
+    name, or chosen from DVEC_MIN windows on where the dimensions allow it."""
+    return precision == "bf16" and dvec_ok(F, H) and (path == "dvec" or (path is None and n_windows >= DVEC_MIN))
+
+
 @torch.no_grad()
 def embed_windows(net, windows, batch=None, precision="f32", path=None, schedule="auto"):
     """Embeddings [S, proj] of windows [S, win, nmels] with the module's weights (GPU), `batch`
@@ -91,18 +103,15 @@ def embed_windows(net, windows, batch=None, precision="f32", path=None, schedule
     (batches of the training forward's persistent recurrences), "dvec" (sv_dvector_embed_bf16, DVEC_CHUNK windows
     per call) or None: "dvec" from DVEC_MIN windows on when no batch is given.  schedule: the
     recurrence schedule of the stack ('auto', 'per_step', 'persist', ...; ops.embedder_forward)."""
-    if precision not in ("f32", "bf16"):
-        raise ValueError(f"precision must be 'f32' or 'bf16', got {precision!r}")
-    if path not in (None, "persist", "dvec") or (path is not None and precision != "bf16"):
-        raise ValueError(f"path must be None, 'persist' or 'dvec' (bf16 only), got {path!r}")
+    _check_path(precision, path)
     dev = next(net.parameters()).device
     layers = net.LSTM_stack.layer_params()
     x = torch.as_tensor(windows, dtype=torch.float32)
     F, H = x.shape[-1], layers[0][1].shape[1]
     if path == "dvec" and not dvec_ok(F, H):
         raise ValueError(f"the per-timestep GEMM path needs F <= 64, H % 64 == 0 and 4H % 256 == 0 (F={F}, H={H})")
-    if precision == "bf16" and (path == "dvec" or (path is None and batch is None and x.shape[0] >= DVEC_MIN
-                                                    and dvec_ok(F, H))):
+    # (a caller's batch size is a request for the batched forward unless it names the path)
+    if _takes_dvec(precision, path, x.shape[0], F, H) and (path == "dvec" or batch is None):
         out = [embedder_forward_dvec_bf16(x[i:i + (batch or DVEC_CHUNK)].to(dev).contiguous(), layers,
                                           net.projection.weight, net.projection.bias)
                for i in range(0, x.shape[0], batch or DVEC_CHUNK)]
@@ -322,8 +331,10 @@ def voiced_ranges(times, n_samples, sr=None):
 
 
 def window_starts(frame_off, win=WIN, hop=HOP):
-    """(starts, counts): the int32 first-row table [S] of every window of every segment -- equal to
-    window_index(frame_off)[:, 0] -- and the number of windows of each segment."""
+    """(starts, counts): the int32 first-row table [S] of every window of every segment -- per
+    segment of T_s frames, j = 0, hop, ... while j + win < T_s (window_frames' rule), segments in
+    order -- and the number of windows of each segment.  The one array form of the rule:
+    window_index is built on it."""
     starts, counts = [], []
     for a, b in zip(frame_off[:-1], frame_off[1:]):
         s = np.arange(0, max(b - a - win, 0), hop, dtype=np.int64)  # j + win < T
@@ -380,10 +391,7 @@ def embed_files(net, files, precision="bf16", path=None, max_samples=2 ** 27, **
     the window tensor stays bounded by the chunk (kw's `batch`, else embed_windows' default).
     Raises PersistentRecurrenceError like embed_windows."""
     from .features import _config, logmel_ranges
-    if precision not in ("f32", "bf16"):
-        raise ValueError(f"precision must be 'f32' or 'bf16', got {precision!r}")
-    if path not in (None, "persist", "dvec") or (path is not None and precision != "bf16"):
-        raise ValueError(f"path must be None, 'persist' or 'dvec' (bf16 only), got {path!r}")
+    _check_path(precision, path)
     _, _, _, hop_n, nmels = _config(None, None, None, None, None)
     layers = net.LSTM_stack.layer_params()
     wp, bp = net.projection.weight, net.projection.bias
@@ -407,7 +415,7 @@ def embed_files(net, files, precision="bf16", path=None, max_samples=2 ** 27, **
         out, _, (win_start, part_off) = logmel_ranges([files[i][0] for i in ids], ranges, tables=tables)
         S = int(win_start.shape[0])
         with torch.cuda.device(out.device):
-            if precision == "bf16" and dvec_ok(nmels, H) and (path == "dvec" or (path is None and S >= DVEC_MIN)):
+            if _takes_dvec(precision, path, S, nmels, H):
                 emb = [embedder_forward_dvec_bf16_frames(out, win_start[i:i + DVEC_CHUNK], layers, wp, bp)
                        for i in range(0, S, DVEC_CHUNK)]
                 check_persistent_status(wait=True)

@@ -38,6 +38,7 @@ already transposed array, with ``librosa.filters.dct``, which librosa removed).
 """
 from __future__ import annotations
 
+import math
 import os
 
 import numpy as np
@@ -115,6 +116,22 @@ def _config(sr, nfft, window, hop, nmels):
     return sr, nfft, win, hop_n, nmels
 
 
+def _frame_table(seg_len, hop, min_len, n_samples, name, noun="segment", rows=128):
+    """frame_off [n + 1] int32 of segments of `seg_len` samples (an int64 array): segment s holds
+    1 + len_s // hop frames (librosa's center=True).  ValueError for a segment shorter than min_len
+    samples (its reflect padding would need a second reflection) and for totals past 32-bit
+    offsets: n_samples samples in the packed buffer or `rows` output scalars per frame.  `name` is
+    the call and `noun` the kind of segment the messages speak of."""
+    short = np.nonzero(seg_len < min_len)[0]
+    if short.size:
+        raise ValueError(f"{noun} {int(short[0])} has {int(seg_len[short[0]])} samples; {name}'s reflect padding "
+                         f"needs at least {min_len}")
+    frame_off = np.concatenate([[0], np.cumsum(1 + seg_len // hop)])
+    if n_samples >= 2 ** 31 or frame_off[-1] * rows >= 2 ** 31:
+        raise ValueError(f"too many samples for one {name} call (32-bit offsets): split the batch")
+    return frame_off.astype(np.int32)
+
+
 def segment_offsets(lengths, nfft, hop):
     """(seg_off, frame_off) of segments of `lengths` samples, as int32 arrays of len + 1: segment s
     holds 1 + len_s // hop frames (librosa's center=True).  ValueError for a segment shorter than
@@ -122,44 +139,36 @@ def segment_offsets(lengths, nfft, hop):
     lengths = np.asarray(lengths, dtype=np.int64)
     if lengths.size == 0:
         raise ValueError("logmel needs at least one segment")
-    short = np.nonzero(lengths < nfft // 2 + 1)[0]
-    if short.size:
-        raise ValueError(f"segment {int(short[0])} has {int(lengths[short[0]])} samples; reflect padding of an "
-                         f"nfft={nfft} STFT needs at least {nfft // 2 + 1}")
     seg_off = np.concatenate([[0], np.cumsum(lengths)])
-    frame_off = np.concatenate([[0], np.cumsum(1 + lengths // hop)])
-    if seg_off[-1] >= 2 ** 31 or frame_off[-1] * 128 >= 2 ** 31:
-        raise ValueError("too many samples for one logmel call (32-bit offsets): split the batch")
-    return seg_off.astype(np.int32), frame_off.astype(np.int32)
+    return seg_off.astype(np.int32), _frame_table(lengths, hop, nfft // 2 + 1, seg_off[-1], "logmel")
 
 
 def _as_list(waves):
-    if isinstance(waves, (list, tuple)):
-        return list(waves)
-    return [waves]
+    return list(waves) if isinstance(waves, (list, tuple)) else [waves]
 
 
-def logmel(waves, sr=None, nfft=None, window=None, hop=None, nmels=None):
-    """Log-mel frames of one waveform segment or a list of them (1-D arrays or tensors, host or
-    device, mono at `sr`): (out [n_frames, nmels] cuda float32, frame_off) with segment s in rows
-    frame_off[s] : frame_off[s + 1].  sr, nfft, window (s), hop (s), nmels default to hp.data.
-    One packed copy in and one kernel launch for the whole batch."""
-    sr, nfft, win, hop_n, nmels = _config(sr, nfft, window, hop, nmels)
+def _waves(waves, noun="waveform"):
+    """One waveform or a list of them, as a list of 1-D arrays or tensors."""
     segs = _as_list(waves)
     for s in segs:
         if getattr(s, "ndim", None) != 1:
-            raise ValueError("each segment must be a 1-D array or tensor of samples")
-    seg_off, frame_off = segment_offsets([int(s.shape[0]) for s in segs], nfft, hop_n)
+            raise ValueError(f"each {noun} must be a 1-D array or tensor of samples")
+    return segs
+
+
+def _pack(segs, seg_off, frame_off):
+    """(y, seg_off, frame_off, device) on the GPU, the one packing of every entry point here: host
+    segments and both offset tables in one pinned buffer and one copy; device-resident segments
+    concatenated there."""
     on_dev = [s for s in segs if torch.is_tensor(s) and s.is_cuda]
-    if on_dev:
-        dev = on_dev[0].device
-    else:
-        dev = _lib.compute_device(torch.empty(0))
-    n, n_seg, n_frames = int(seg_off[-1]), len(segs), int(frame_off[-1])
+    dev = on_dev[0].device if on_dev else _lib.compute_device(torch.empty(0))
+    n, n_seg = int(seg_off[-1]), len(segs)
     offs = np.concatenate([seg_off, frame_off])
     if on_dev:
         y = torch.cat([torch.as_tensor(s).to(dev, torch.float32) for s in segs]) if n_seg > 1 else \
             on_dev[0].to(torch.float32).contiguous()
+        if y.data_ptr() % 16:  # a slice of a larger tensor: the entry points want 16-byte alignment
+            y = y.clone()
         o = torch.from_numpy(offs).to(dev)
     else:
         # samples and both offset tables in one pinned buffer: one host-to-device copy
@@ -172,10 +181,31 @@ def logmel(waves, sr=None, nfft=None, window=None, hop=None, nmels=None):
         hn[npad:].view(np.int32)[:] = offs
         buf = host.to(dev, non_blocking=True)
         y, o = buf[:n], buf[npad:].view(torch.int32)
+    return y, o[:n_seg + 1], o[n_seg + 1:], dev
+
+
+def _stft_launch(into, y, tabs, n_seg, shape, cfg, dev, *extra):
+    """out [*shape, nmels] (math.prod(shape) frames) of one of the three STFT entry points: the
+    (wbasis, melfb) tables, the output buffer and into(y, *tabs, n_seg, n_frames, configuration,
+    tables, out, *extra) on dev."""
+    sr, nfft, win, hop_n, nmels = cfg
     wbasis, melfb = stft_tables(sr, nfft, win, nmels, dev)
-    out = torch.empty((n_frames, nmels), dtype=torch.float32, device=dev)
+    out = torch.empty((*shape, nmels), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        logmel_into(y, o[:n_seg + 1], o[n_seg + 1:], n_seg, n_frames, nfft, win, hop_n, nmels, wbasis, melfb, out)
+        into(y, *tabs, n_seg, math.prod(shape), nfft, win, hop_n, nmels, wbasis, melfb, out, *extra)
+    return out
+
+
+def logmel(waves, sr=None, nfft=None, window=None, hop=None, nmels=None):
+    """Log-mel frames of one waveform segment or a list of them (1-D arrays or tensors, host or
+    device, mono at `sr`): (out [n_frames, nmels] cuda float32, frame_off) with segment s in rows
+    frame_off[s] : frame_off[s + 1].  sr, nfft, window (s), hop (s), nmels default to hp.data.
+    One packed copy in and one kernel launch for the whole batch."""
+    cfg = _config(sr, nfft, window, hop, nmels)
+    segs = _waves(waves, "segment")
+    seg_off, frame_off = segment_offsets([int(s.shape[0]) for s in segs], cfg[1], cfg[3])
+    y, so, fo, dev = _pack(segs, seg_off, frame_off)
+    out = _stft_launch(logmel_into, y, (so, fo), len(segs), (int(frame_off[-1]),), cfg, dev)
     return out, [int(v) for v in frame_off]
 
 
@@ -204,15 +234,9 @@ def range_tables(lengths, ranges, nfft, hop):
         k = int(bad[0])
         raise ValueError(f"range {k} [{int(r[k, 1])}, {int(r[k, 2])}) lies outside its waveform of {int(n[k])} samples")
     seg_len = r[:, 2] - r[:, 1]
-    short = np.nonzero(seg_len < nfft // 2 + 1)[0]
-    if short.size:
-        raise ValueError(f"range {int(short[0])} has {int(seg_len[short[0]])} samples; reflect padding of an "
-                         f"nfft={nfft} STFT needs at least {nfft // 2 + 1}")
     seg_off = np.concatenate([[0], np.cumsum(lengths)])
-    frame_off = np.concatenate([[0], np.cumsum(1 + seg_len // hop)])
-    if seg_off[-1] >= 2 ** 31 or frame_off[-1] * 128 >= 2 ** 31:
-        raise ValueError("too many samples for one logmel_ranges call (32-bit offsets): split the batch")
-    return (seg_off[r[:, 0]] + r[:, 1]).astype(np.int32), seg_len.astype(np.int32), frame_off.astype(np.int32)
+    frame_off = _frame_table(seg_len, hop, nfft // 2 + 1, seg_off[-1], "logmel_ranges", "range")
+    return (seg_off[r[:, 0]] + r[:, 1]).astype(np.int32), seg_len.astype(np.int32), frame_off
 
 
 def logmel_ranges(y, ranges, sr=None, nfft=None, window=None, hop=None, nmels=None, tables=None):
@@ -226,23 +250,17 @@ def logmel_ranges(y, ranges, sr=None, nfft=None, window=None, hop=None, nmels=No
     offsets.  `tables` (a callable frame_off -> list of int32 arrays) rides in the same upload; with
     it the result is (out, frame_off, [the arrays on the device]) -- dvector.embed_files sends its
     window and partition tables this way."""
-    sr, nfft, win, hop_n, nmels = _config(sr, nfft, window, hop, nmels)
-    waves = _as_list(y)
-    for s in waves:
-        if getattr(s, "ndim", None) != 1:
-            raise ValueError("each waveform must be a 1-D array or tensor of samples")
+    cfg = _config(sr, nfft, window, hop, nmels)
+    waves = _waves(y)
     lengths = [int(s.shape[0]) for s in waves]
-    seg_start, seg_len, frame_off = range_tables(lengths, ranges, nfft, hop_n)
+    seg_start, seg_len, frame_off = range_tables(lengths, ranges, cfg[1], cfg[3])
     frame_off_l = [int(v) for v in frame_off]
     extra = [np.ascontiguousarray(t, dtype=np.int32) for t in tables(frame_off_l)] if tables is not None else []
     n_seg, n_frames = len(seg_len), frame_off_l[-1]
     seg_off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
     y_dev, _, tab, dev = _pack(waves, seg_off, np.concatenate([seg_start, seg_len, frame_off] + extra))
-    wbasis, melfb = stft_tables(sr, nfft, win, nmels, dev)
-    out = torch.empty((n_frames, nmels), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        logmel_ranges_into(y_dev, tab[:n_seg], tab[n_seg:2 * n_seg], tab[2 * n_seg:3 * n_seg + 1], n_seg, n_frames, nfft,
-                           win, hop_n, nmels, wbasis, melfb, out)
+    out = _stft_launch(logmel_ranges_into, y_dev, (tab[:n_seg], tab[n_seg:2 * n_seg], tab[2 * n_seg:3 * n_seg + 1]),
+                       n_seg, (n_frames,), cfg, dev)
     if tables is None:
         return out, frame_off_l
     pos, on_dev = 3 * n_seg + 1, []
@@ -280,32 +298,6 @@ def preprocess_utterance(utter, intervals, tisv_frame=None):
     return specs
 
 
-def _pack(segs, seg_off, frame_off):
-    """(y, seg_off, frame_off, device) on the GPU, as logmel packs them: host segments and both
-    offset tables in one pinned buffer and one copy; device-resident segments concatenated there."""
-    on_dev = [s for s in segs if torch.is_tensor(s) and s.is_cuda]
-    dev = on_dev[0].device if on_dev else _lib.compute_device(torch.empty(0))
-    n, n_seg = int(seg_off[-1]), len(segs)
-    offs = np.concatenate([seg_off, frame_off])
-    if on_dev:
-        y = torch.cat([torch.as_tensor(s).to(dev, torch.float32) for s in segs]) if n_seg > 1 else \
-            on_dev[0].to(torch.float32).contiguous()
-        if y.data_ptr() % 16:  # a slice of a larger tensor: the entry points want 16-byte alignment
-            y = y.clone()
-        o = torch.from_numpy(offs).to(dev)
-    else:
-        npad = (n + 3) // 4 * 4
-        host = torch.empty(npad + offs.size, dtype=torch.float32, pin_memory=True)
-        hn = host.numpy()
-        for s, a in zip(segs, seg_off[:-1]):
-            hn[a:a + s.shape[0]] = s.numpy() if torch.is_tensor(s) else np.asarray(s)
-        hn[n:npad] = 0.0
-        hn[npad:].view(np.int32)[:] = offs
-        buf = host.to(dev, non_blocking=True)
-        y, o = buf[:n], buf[npad:].view(torch.int32)
-    return y, o[:n_seg + 1], o[n_seg + 1:], dev
-
-
 def energy_offsets(lengths, frame_length, hop_length):
     """(seg_off, frame_off) int32 arrays of len + 1 for waveforms of `lengths` samples: waveform s
     holds 1 + len_s // hop_length energy frames.  ValueError for an odd frame_length, a hop below 1
@@ -316,15 +308,10 @@ def energy_offsets(lengths, frame_length, hop_length):
     lengths = np.asarray(lengths, dtype=np.int64)
     if lengths.size == 0:
         raise ValueError("frame_energy needs at least one waveform")
-    short = np.nonzero(lengths < frame_length // 2 + 1)[0]
-    if short.size:
-        raise ValueError(f"waveform {int(short[0])} has {int(lengths[short[0]])} samples; reflect padding of "
-                         f"frame_length={frame_length} needs at least {frame_length // 2 + 1}")
     seg_off = np.concatenate([[0], np.cumsum(lengths)])
-    frame_off = np.concatenate([[0], np.cumsum(1 + lengths // hop_length)])
-    if seg_off[-1] >= 2 ** 31:
-        raise ValueError("too many samples for one frame_energy call (32-bit offsets): split the batch")
-    return seg_off.astype(np.int32), frame_off.astype(np.int32)
+    # (rows=1: mse holds one scalar per frame)
+    return seg_off.astype(np.int32), _frame_table(lengths, hop_length, frame_length // 2 + 1, seg_off[-1],
+                                                  "frame_energy", "waveform", rows=1)
 
 
 def frame_energy(waves, frame_length=2048, hop_length=512):
@@ -332,10 +319,7 @@ def frame_energy(waves, frame_length=2048, hop_length=512):
     or a list of them (1-D arrays or tensors, host or device): (mse [n_frames] cuda float32,
     frame_off) with waveform s in mse[frame_off[s] : frame_off[s + 1]].  One packed copy in and one
     kernel launch for the whole batch; a waveform's values do not depend on its neighbours."""
-    segs = _as_list(waves)
-    for s in segs:
-        if getattr(s, "ndim", None) != 1:
-            raise ValueError("each waveform must be a 1-D array or tensor of samples")
+    segs = _waves(waves)
     seg_off, frame_off = energy_offsets([int(s.shape[0]) for s in segs], frame_length, hop_length)
     y, so, fo, dev = _pack(segs, seg_off, frame_off)
     n_frames = int(frame_off[-1])
@@ -366,7 +350,7 @@ def split(waves, top_db=60, frame_length=2048, hop_length=512):
     """librosa.effects.split: the non-silent [start, end) sample intervals of one waveform ([k, 2]
     int64, k may be 0) or of each waveform of a list (a list of such arrays).  Every waveform is
     measured against its own loudest frame.  One launch and one device-to-host copy per call."""
-    segs = _as_list(waves)
+    segs = _as_list(waves)  # (frame_energy checks them)
     mse, frame_off = frame_energy(segs, frame_length, hop_length)
     mse = mse.cpu().numpy()
     out = [intervals_from_energy(mse[a:b], int(s.shape[0]), hop_length, top_db)
@@ -374,11 +358,15 @@ def split(waves, top_db=60, frame_length=2048, hop_length=512):
     return out if isinstance(waves, (list, tuple)) else out[0]
 
 
+def _trim_bounds(intervals):
+    """trim's (start, end) from split's intervals: the first one's start and the last one's end."""
+    return (int(intervals[0, 0]), int(intervals[-1, 1])) if len(intervals) else (0, 0)
+
+
 def trim(wave, top_db=60, frame_length=2048, hop_length=512):
     """librosa.effects.trim: (wave[start:end], (start, end)) from the first non-silent interval's
     start to the last one's end; (0, 0) if no frame is non-silent."""
-    iv = split(wave, top_db, frame_length, hop_length)
-    start, end = (int(iv[0, 0]), int(iv[-1, 1])) if len(iv) else (0, 0)
+    start, end = _trim_bounds(split(wave, top_db, frame_length, hop_length))
     return wave[start:end], (start, end)
 
 
@@ -397,23 +385,17 @@ def mel_db(waves, sr=None, nfft=None, window=None, hop=None, nmels=None, amin=1e
     20 log10(max(amin, .)), then nothing below the segment's own maximum - top_db (top_db=None: no
     clip).  One packed copy in and one sv_meldb call for the whole batch; a segment's values do not
     depend on its neighbours.  Decoding, resampling, mag_db and calc_mfccs are out of scope."""
-    sr, nfft, win, hop_n, nmels = _config(sr, nfft, window, hop, nmels)
+    cfg = _config(sr, nfft, window, hop, nmels)
     amin, top_db = _check_db(amin, top_db)
-    segs = _as_list(waves)
-    for s in segs:
-        if getattr(s, "ndim", None) != 1:
-            raise ValueError("each segment must be a 1-D array or tensor of samples")
-    seg_off, frame_off = segment_offsets([int(s.shape[0]) for s in segs], nfft, hop_n)
+    segs = _waves(waves, "segment")
+    seg_off, frame_off = segment_offsets([int(s.shape[0]) for s in segs], cfg[1], cfg[3])
     n_seg, n_frames = len(segs), int(frame_off[-1])
     # the lengths ride behind frame_off in _pack's one copy: seg_valid = seg_len = the real lengths
     y, so, fo, dev = _pack(segs, seg_off, np.concatenate([frame_off, np.diff(seg_off)]).astype(np.int32))
     lengths = fo[n_seg + 1:]
-    wbasis, melfb = stft_tables(sr, nfft, win, nmels, dev)
-    out = torch.empty((n_frames, nmels), dtype=torch.float32, device=dev)
     seg_max = torch.empty(n_seg, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        mel_db_into(y, so[:n_seg], lengths, lengths, fo[:n_seg + 1], n_seg, n_frames, nfft, win, hop_n, nmels, wbasis,
-                    melfb, out, seg_max, amin, top_db)
+    out = _stft_launch(mel_db_into, y, (so[:n_seg], lengths, lengths, fo[:n_seg + 1]), n_seg, (n_frames,), cfg, dev,
+                       seg_max, amin, top_db)
     return out, [int(v) for v in frame_off]
 
 
@@ -444,10 +426,10 @@ def fixed_segments(bounds, seg_off, length, hop):
     n = len(bounds)
     start = np.asarray(seg_off, dtype=np.int64)[:n] + bounds[:, 0]
     valid = np.minimum(bounds[:, 1] - bounds[:, 0], length)
-    frame_off = np.arange(n + 1, dtype=np.int64) * (1 + length // hop)
-    if frame_off[-1] * 128 >= 2 ** 31:
-        raise ValueError("too many frames for one mel_db_fixed call (32-bit offsets): split the batch")
-    return np.concatenate([start, valid, np.full(n, length, dtype=np.int64), frame_off]).astype(np.int32)
+    seg_len = np.full(n, length, dtype=np.int64)
+    # (no minimum here: mel_db_fixed checks `length` itself; the samples stay where _pack put them)
+    frame_off = _frame_table(seg_len, hop, 0, 0, "mel_db_fixed")
+    return np.concatenate([start, valid, seg_len, frame_off]).astype(np.int32)
 
 
 def mel_db_fixed(waves, length=None, trim_top_db=60, amin=1e-5, top_db=80.0):
@@ -463,15 +445,12 @@ def mel_db_fixed(waves, length=None, trim_top_db=60, amin=1e-5, top_db=80.0):
     call: trim, zero padding and truncation are that table's index arithmetic, the audio is never
     copied or re-packed on the device.  ValueError for a waveform shorter than win // 2 + 1 samples
     (the trim's reflection) or a length below nfft // 2 + 1 (the STFT's)."""
-    sr, nfft, win, hop_n, nmels = _config(None, None, None, None, None)
+    cfg = _, nfft, win, hop_n, nmels = _config(None, None, None, None, None)
     amin, top_db = _check_db(amin, top_db)
     length = fixed_length(length)
     if length < nfft // 2 + 1:
         raise ValueError(f"length={length}; reflect padding of an nfft={nfft} STFT needs at least {nfft // 2 + 1}")
-    segs = _as_list(waves)
-    for s in segs:
-        if getattr(s, "ndim", None) != 1:
-            raise ValueError("each waveform must be a 1-D array or tensor of samples")
+    segs = _waves(waves)
     lengths = [int(s.shape[0]) for s in segs]
     seg_off, efo = energy_offsets(lengths, win, hop_n)  # (ValueError for a waveform shorter than win // 2 + 1)
     y, so, fo, dev = _pack(segs, seg_off, efo)
@@ -483,17 +462,13 @@ def mel_db_fixed(waves, length=None, trim_top_db=60, amin=1e-5, top_db=80.0):
             mse = torch.empty(int(efo[-1]), dtype=torch.float32, device=dev)
             frame_energy_into(y, so, fo, n, int(efo[-1]), win, hop_n, mse)
             mse = mse.cpu().numpy()
-            bounds = []
-            for m, a, b in zip(lengths, efo[:-1], efo[1:]):
-                iv = intervals_from_energy(mse[a:b], m, hop_n, trim_top_db)
-                bounds.append((int(iv[0, 0]), int(iv[-1, 1])) if len(iv) else (0, 0))
+            bounds = [_trim_bounds(intervals_from_energy(mse[a:b], m, hop_n, trim_top_db))
+                      for m, a, b in zip(lengths, efo[:-1], efo[1:])]
         table = torch.from_numpy(fixed_segments(bounds, seg_off, length, hop_n)).pin_memory().to(dev, non_blocking=True)
         T = 1 + length // hop_n
-        wbasis, melfb = stft_tables(sr, nfft, win, nmels, dev)
-        out = torch.empty((n, T, nmels), dtype=torch.float32, device=dev)
         seg_max = torch.empty(n, dtype=torch.float32, device=dev)
-        mel_db_into(y, table[:n], table[n:2 * n], table[2 * n:3 * n], table[3 * n:], n, n * T, nfft, win, hop_n, nmels,
-                    wbasis, melfb, out, seg_max, amin, top_db)
+        out = _stft_launch(mel_db_into, y, (table[:n], table[n:2 * n], table[2 * n:3 * n], table[3 * n:]), n, (n, T),
+                           cfg, dev, seg_max, amin, top_db)
     return out
 
 
@@ -537,8 +512,6 @@ def preprocess_speaker(utterances, top_db=30, tisv_frame=None):
                 segs.append(part)
     if not segs:
         return np.zeros((0, nmels, tisv), dtype=np.float32)
-    if len(segs) == 1 and torch.is_tensor(segs[0]) and segs[0].is_cuda:
-        segs[0] = segs[0].clone()  # (a lone device-resident slice: logmel takes it as it is, aligned or not)
     out, frame_off = logmel(segs)
     rows = np.array([frame_off[s] + f for s, f in picks], dtype=np.int64)[:, None] + np.arange(tisv)[None, :]
     spec = out[torch.from_numpy(rows).to(out.device)].transpose(1, 2).contiguous()  # [K, nmels, tisv]

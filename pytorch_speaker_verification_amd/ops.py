@@ -406,25 +406,36 @@ def embedder_forward_bf16(x, layers, w_p, b_p, save=True, status=None, probe=Non
     return _proj_norm_fwd(st, hs[-1][T], w_p, b_p, s), st
 
 
+def _dvec_bf16(entry, src, B, T, F, layers, w_p, b_p):
+    """The shared body of the two sv_dvector_embed_bf16* wrappers: `src` is the entry point's input
+    arguments (between L and the weight arrays), a tuple of tensors and ints whose first member
+    gives the device and the stream."""
+    require_device(src[0], w_p, *[t for l in layers for t in l if t is not None])
+    H = layers[0][1].shape[1]
+    P = w_p.shape[0]
+    L = len(layers)
+    emb = torch.empty((B, P), dtype=torch.float32, device=src[0].device)
+    ws = _ws(lib().sv_dvector_bf16_workspace(B, T, F, H, L, P), src[0].device)
+    ts = [[l[i].contiguous() if l[i] is not None else None for l in layers] for i in range(4)]  # kept alive
+    wih, whh, bih, bhh = (_parr(t) for t in ts)
+    call(entry, B, T, F, H, L, *[ptr(a) if torch.is_tensor(a) else a for a in src], wih, whh, bih, bhh,
+         ptr(w_p.contiguous()), ptr(b_p) if b_p is not None else None, P, ptr(emb), ptr(ws), stream_of(src[0]))
+    return emb
+
+
 def embedder_forward_dvec_bf16(x, layers, w_p, b_p):
     """Embeddings [B, P] of B windows x [B, T, F] (fp32, batch-first) by sv_dvector_embed_bf16:
     the c3 forward's numerics (bf16 GEMM operands, bf16 input projection with its biases, fp32
     accumulation / state / projection) as one 256 x 256 GEMM launch per timestep and layer with the
     LSTM cell in its epilogue -- the large-batch d-vector path (dvector_create.py:96-101), no
     activations saved and no co-residency requirement."""
-    require_device(x, w_p, *[t for l in layers for t in l if t is not None])
     B, T, F = x.shape
-    H = layers[0][1].shape[1]
-    P = w_p.shape[0]
-    L = len(layers)
-    x = x.contiguous()
-    emb = torch.empty((B, P), dtype=torch.float32, device=x.device)
-    ws = _ws(lib().sv_dvector_bf16_workspace(B, T, F, H, L, P), x.device)
-    ts = [[l[i].contiguous() if l[i] is not None else None for l in layers] for i in range(4)]  # kept alive
-    wih, whh, bih, bhh = (_parr(t) for t in ts)
-    call("sv_dvector_embed_bf16", B, T, F, H, L, ptr(x), wih, whh, bih, bhh, ptr(w_p.contiguous()),
-         ptr(b_p) if b_p is not None else None, P, ptr(emb), ptr(ws), stream_of(x))
-    return emb
+    return _dvec_bf16("sv_dvector_embed_bf16", (x.contiguous(),), B, T, F, layers, w_p, b_p)
+
+
+def _check_i32_table(t, name):
+    if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 1:
+        raise RuntimeError(f"{name} must be a contiguous 1-D int32 tensor on the GPU")
 
 
 def embedder_forward_dvec_bf16_frames(frames, win_start, layers, w_p, b_p):
@@ -435,21 +446,10 @@ def embedder_forward_dvec_bf16_frames(frames, win_start, layers, w_p, b_p):
     built; the embeddings [B, P] are bit-identical to embedder_forward_dvec_bf16 on the
     materialised windows at the same B."""
     from .dvector import WIN
-    require_device(frames, w_p, *[t for l in layers for t in l if t is not None])
-    if not win_start.is_cuda or win_start.dtype != torch.int32 or not win_start.is_contiguous() or win_start.dim() != 1:
-        raise RuntimeError("win_start must be a contiguous 1-D int32 tensor on the GPU")
+    _check_i32_table(win_start, "win_start")
     n_rows, F = frames.shape
-    B, T = win_start.shape[0], WIN
-    H = layers[0][1].shape[1]
-    P = w_p.shape[0]
-    L = len(layers)
-    emb = torch.empty((B, P), dtype=torch.float32, device=frames.device)
-    ws = _ws(lib().sv_dvector_bf16_workspace(B, T, F, H, L, P), frames.device)
-    ts = [[l[i].contiguous() if l[i] is not None else None for l in layers] for i in range(4)]  # kept alive
-    wih, whh, bih, bhh = (_parr(t) for t in ts)
-    call("sv_dvector_embed_bf16_frames", B, T, F, H, L, ptr(frames), n_rows, ptr(win_start), wih, whh, bih, bhh,
-         ptr(w_p.contiguous()), ptr(b_p) if b_p is not None else None, P, ptr(emb), ptr(ws), stream_of(frames))
-    return emb
+    return _dvec_bf16("sv_dvector_embed_bf16_frames", (frames, n_rows, win_start), win_start.shape[0], WIN, F, layers,
+                      w_p, b_p)
 
 
 def dvec_align(emb, part_off):
@@ -457,8 +457,7 @@ def dvec_align(emb, part_off):
     float64 on the device (sv_dvec_align; part_off a device int32 tensor of n_parts + 1 offsets):
     equal to np.average of each float32 row block, i.e. to dvector.align_embeddings, exactly."""
     require_device(emb)
-    if not part_off.is_cuda or part_off.dtype != torch.int32 or not part_off.is_contiguous() or part_off.dim() != 1:
-        raise RuntimeError("part_off must be a contiguous 1-D int32 tensor on the GPU")
+    _check_i32_table(part_off, "part_off")
     S, P = emb.shape
     n_parts = part_off.shape[0] - 1
     out = torch.empty((n_parts, P), dtype=torch.float64, device=emb.device)

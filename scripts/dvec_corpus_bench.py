@@ -22,9 +22,7 @@ Needs a GPU.
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
@@ -34,6 +32,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 from pytorch_speaker_verification_amd import dvector, features, ops  # noqa: E402
 from pytorch_speaker_verification_amd.hparam import hparam as hp  # noqa: E402
+from _timing import timed_events, timed_host  # noqa: E402
 
 SR = 16000
 
@@ -66,17 +65,9 @@ def make_net():
     return net.cuda()
 
 
-def timed_host(fn, repeats, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(repeats):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ms.append((time.perf_counter() - t0) * 1e3)
-    return {"median": round(statistics.median(ms), 2), "min": round(min(ms), 2), "max": round(max(ms), 2)}
+def timed_ms(fn, repeats, warmup):
+    t = timed_host(fn, repeats, warmup)
+    return {"median": round(t[0], 2), "min": round(t[1], 2), "max": round(t[2], 2)}
 
 
 def stages(net, files, precision):
@@ -120,17 +111,12 @@ def logmel_ranges_kernel(files, repeats):
     t = [torch.from_numpy(v).cuda() for v in (seg_start, seg_len, frame_off)]
     wbasis, melfb = features.stft_tables(sr, nfft, win, nmels, y.device)
     out = torch.empty((int(frame_off[-1]), nmels), dtype=torch.float32, device=y.device)
-    ms = []
-    for i in range(repeats + 2):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        features.logmel_ranges_into(y, t[0], t[1], t[2], len(ranges), out.shape[0], nfft, win, hop_n, nmels, wbasis, melfb,
-                                    out)
-        b.record()
-        b.synchronize()
-        if i >= 2:
-            ms.append(a.elapsed_time(b))
-    return round(statistics.median(ms), 3)
+
+    def kernel():
+        features.logmel_ranges_into(y, t[0], t[1], t[2], len(ranges), out.shape[0], nfft, win, hop_n, nmels, wbasis,
+                                    melfb, out)
+
+    return round(timed_events(kernel, repeats, 2)[0], 3)
 
 
 def main():
@@ -167,9 +153,9 @@ def main():
 
         got, ref = whole(), per_file()
         r = {"max_abs_corpus_vs_per_file": float(max(np.abs(g - p).max() for g, p in zip(got, ref)))}
-        r["corpus_ms"] = timed_host(whole, args.repeats, args.warmup)
-        r["per_file_ms"] = timed_host(per_file, args.repeats, args.warmup)
-        r["per_file_graph_ms"] = timed_host(per_file_graph, args.repeats, args.warmup)
+        r["corpus_ms"] = timed_ms(whole, args.repeats, args.warmup)
+        r["per_file_ms"] = timed_ms(per_file, args.repeats, args.warmup)
+        r["per_file_graph_ms"] = timed_ms(per_file_graph, args.repeats, args.warmup)
         stages(net, files, precision)  # warm-up
         r["stages"] = stages(net, files, precision)
         r["per_file_over_corpus"] = round(r["per_file_ms"]["median"] / r["corpus_ms"]["median"], 2)

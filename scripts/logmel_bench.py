@@ -19,15 +19,14 @@ and the largest difference between the two results.  Prints one JSON line.  Need
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pytorch_speaker_verification_amd import features  # noqa: E402
+from _timing import timed_events, timed_host  # noqa: E402
 
 SR, NFFT, WIN, HOP, NMELS = 16000, 512, 400, 160, 40
 
@@ -47,36 +46,6 @@ def torch_logmel(segs, window, melfb_t):
         P = S.real.square() + S.imag.square()  # [nb, T]
         outs.append(torch.log10(P.t() @ melfb_t + 1e-6))
     return torch.cat(outs)
-
-
-def timed_events(fn, calls, repeats, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(calls):
-            fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b) / calls)
-    return statistics.median(ms), min(ms), max(ms)
-
-
-def timed_host(fn, calls, repeats, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(repeats):
-        t0 = time.perf_counter()
-        for _ in range(calls):
-            fn()
-        torch.cuda.synchronize()
-        ms.append((time.perf_counter() - t0) * 1e3 / calls)
-    return statistics.median(ms), min(ms), max(ms)
 
 
 def main():
@@ -111,11 +80,11 @@ def main():
         ref = torch_logmel(dsegs, window, melfb_t)
         diff = float((got - ref).abs().max())
         r = {"segments": len(segs), "frames": n_frames, "calls_per_window": calls, "max_abs_hip_vs_torch": diff}
-        for key, t in (("hip_host", timed_host(lambda: features.logmel(segs), calls, args.repeats, args.warmup)),
-                       ("hip_dev", timed_events(lambda: features.logmel(dsegs), calls, args.repeats, args.warmup)),
-                       ("hip_kernel", timed_events(kernel, calls, args.repeats, args.warmup)),
-                       ("torch_dev", timed_events(lambda: torch_logmel(dsegs, window, melfb_t), calls, args.repeats,
-                                                  args.warmup))):
+        for key, t in (("hip_host", timed_host(lambda: features.logmel(segs), args.repeats, args.warmup, calls)),
+                       ("hip_dev", timed_events(lambda: features.logmel(dsegs), args.repeats, args.warmup, calls)),
+                       ("hip_kernel", timed_events(kernel, args.repeats, args.warmup, calls)),
+                       ("torch_dev", timed_events(lambda: torch_logmel(dsegs, window, melfb_t), args.repeats,
+                                                  args.warmup, calls))):
             r[key + "_ms"] = {"median": round(t[0], 4), "min": round(t[1], 4), "max": round(t[2], 4)}
         # the fused kernel's arithmetic: frames x (2 nb columns) x win taps, 2 flops each, + the mel product
         flops = 2.0 * n_frames * (NFFT + 2) * WIN + 2.0 * n_frames * (NFFT // 2 + 1) * NMELS

@@ -26,15 +26,14 @@ and the largest difference between the HIP result and torch's.  Prints one JSON 
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pytorch_speaker_verification_amd import features  # noqa: E402
+from _timing import timed_events, timed_host  # noqa: E402
 
 SR, NFFT, WIN, HOP, NMELS, LENGTH = 16000, 512, 400, 160, 40, 29200
 AMIN, TOP_DB = 1e-5, 80.0
@@ -56,36 +55,6 @@ def torch_meldb(batch, window, melfb_t):
     x = S.abs().transpose(1, 2) @ melfb_t  # [n, T, nmels]
     db = 20.0 * torch.log10(torch.clamp(x, min=AMIN))
     return torch.maximum(db, db.amax(dim=(1, 2), keepdim=True) - TOP_DB)
-
-
-def timed_events(fn, calls, repeats, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(calls):
-            fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b) / calls)
-    return statistics.median(ms), min(ms), max(ms)
-
-
-def timed_host(fn, calls, repeats, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(repeats):
-        t0 = time.perf_counter()
-        for _ in range(calls):
-            fn()
-        torch.cuda.synchronize()
-        ms.append((time.perf_counter() - t0) * 1e3 / calls)
-    return statistics.median(ms), min(ms), max(ms)
 
 
 def main():
@@ -136,15 +105,15 @@ def main():
         padded = sum(1 for a, b in bounds if b - a < LENGTH)
         r = {"utterances": n, "frames": n * T, "padded": padded, "truncated": n - padded, "calls_per_window": calls,
              "max_abs_hip_vs_torch_db": diff}
-        for key, t in (("fixed_host", timed_host(lambda: features.mel_db_fixed(waves, length=LENGTH), calls,
-                                                 args.repeats, args.warmup)),
-                       ("fixed_dev", timed_host(lambda: features.mel_db_fixed(dwaves, length=LENGTH), calls,
-                                                args.repeats, args.warmup)),
-                       ("meldb_call", timed_events(lambda: meldb(TOP_DB), calls, args.repeats, args.warmup)),
-                       ("meldb_noclip", timed_events(lambda: meldb(-1.0), calls, args.repeats, args.warmup)),
-                       ("logmel_kernel", timed_events(logmel, calls, args.repeats, args.warmup)),
-                       ("torch_dev", timed_events(lambda: torch_meldb(batch, window, melfb_t), calls, args.repeats,
-                                                  args.warmup))):
+        for key, t in (("fixed_host", timed_host(lambda: features.mel_db_fixed(waves, length=LENGTH), args.repeats,
+                                                 args.warmup, calls)),
+                       ("fixed_dev", timed_host(lambda: features.mel_db_fixed(dwaves, length=LENGTH), args.repeats,
+                                                args.warmup, calls)),
+                       ("meldb_call", timed_events(lambda: meldb(TOP_DB), args.repeats, args.warmup, calls)),
+                       ("meldb_noclip", timed_events(lambda: meldb(-1.0), args.repeats, args.warmup, calls)),
+                       ("logmel_kernel", timed_events(logmel, args.repeats, args.warmup, calls)),
+                       ("torch_dev", timed_events(lambda: torch_meldb(batch, window, melfb_t), args.repeats,
+                                                  args.warmup, calls))):
             r[key + "_ms"] = {"median": round(t[0], 4), "min": round(t[1], 4), "max": round(t[2], 4)}
         r["clip_kernel_ms"] = round(r["meldb_call_ms"]["median"] - r["meldb_noclip_ms"]["median"], 4)
         r["torch_over_meldb_call"] = round(r["torch_dev_ms"]["median"] / r["meldb_call_ms"]["median"], 2)

@@ -20,15 +20,14 @@ and the largest relative difference between the two results.  Prints one JSON li
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pytorch_speaker_verification_amd import features  # noqa: E402
+from _timing import timed_events, timed_host  # noqa: E402
 
 SR, FRAME, HOP = 16000, 2048, 512
 
@@ -44,36 +43,6 @@ def torch_energy(waves):
         p = torch.nn.functional.pad(y[None, None, :], (FRAME // 2, FRAME // 2), mode="reflect")[0, 0]
         outs.append(p.unfold(0, FRAME, HOP).square().mean(dim=1))
     return torch.cat(outs)
-
-
-def timed_events(fn, calls, repeats, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(calls):
-            fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b) / calls)
-    return statistics.median(ms), min(ms), max(ms)
-
-
-def timed_host(fn, calls, repeats, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(repeats):
-        t0 = time.perf_counter()
-        for _ in range(calls):
-            fn()
-        torch.cuda.synchronize()
-        ms.append((time.perf_counter() - t0) * 1e3 / calls)
-    return statistics.median(ms), min(ms), max(ms)
 
 
 def main():
@@ -105,11 +74,12 @@ def main():
         ref = torch_energy(dwaves)
         diff = float(((got - ref).abs() / ref).max())
         r = {"waveforms": len(waves), "frames": n_frames, "calls_per_window": calls, "max_rel_hip_vs_torch": diff}
-        for key, t in (("split_host", timed_host(lambda: features.split(waves, top_db=30), calls, args.repeats,
-                                                 args.warmup)),
-                       ("hip_dev", timed_events(lambda: features.frame_energy(dwaves), calls, args.repeats, args.warmup)),
-                       ("hip_kernel", timed_events(kernel, calls, args.repeats, args.warmup)),
-                       ("torch_dev", timed_events(lambda: torch_energy(dwaves), calls, args.repeats, args.warmup))):
+        for key, t in (("split_host", timed_host(lambda: features.split(waves, top_db=30), args.repeats,
+                                                 args.warmup, calls)),
+                       ("hip_dev", timed_events(lambda: features.frame_energy(dwaves), args.repeats, args.warmup,
+                                                calls)),
+                       ("hip_kernel", timed_events(kernel, args.repeats, args.warmup, calls)),
+                       ("torch_dev", timed_events(lambda: torch_energy(dwaves), args.repeats, args.warmup, calls))):
             r[key + "_ms"] = {"median": round(t[0], 4), "min": round(t[1], 4), "max": round(t[2], 4)}
         # every frame reads frame_length samples (from L2 after the first touch)
         r["hip_kernel_read_gbs"] = round(4.0 * n_frames * FRAME / (r["hip_kernel_ms"]["median"] * 1e-3) / 1e9, 1)

@@ -69,13 +69,17 @@ def dft_basis(nfft, win):
     return w * np.cos(ang), w * np.sin(ang)
 
 
-def power_ref(y, sr=16000, nfft=512, window=0.025, hop=0.01, dtype=np.float64):
-    """P [n_frames, nfft//2 + 1] in `dtype`."""
+def spectrum_ref(y, sr=16000, nfft=512, window=0.025, hop=0.01, dtype=np.float64):
+    """(re, im) of the STFT, [n_frames, nfft//2 + 1] each, in `dtype`."""
     win, hp_, _ = sizes(sr, nfft, window, hop)
     fr = frames_of(np.asarray(y, dtype=np.float64), nfft, win, hp_).astype(dtype)
     c, s = dft_basis(nfft, win)
-    re = fr @ c.astype(dtype)
-    im = fr @ s.astype(dtype)
+    return fr @ c.astype(dtype), fr @ s.astype(dtype)
+
+
+def power_ref(y, sr=16000, nfft=512, window=0.025, hop=0.01, dtype=np.float64):
+    """P [n_frames, nfft//2 + 1] in `dtype`."""
+    re, im = spectrum_ref(y, sr, nfft, window, hop, dtype)
     return re * re + im * im
 
 
@@ -111,9 +115,9 @@ def burst(n=8000, start=3000, length=2000, sr=16000):
     return y
 
 
-def err_bound(y, factor=6.0, **cfg):
+def err_bound(y, factor=6.0, ref_fn=logmel_ref, **cfg):
     """(reference fp64 [n_frames, nmels], bound): bound = factor x the largest error the fp32 CPU
-    evaluation of the same definition makes against fp64 on this input."""
-    ref = logmel_ref(y, **cfg)
-    f32 = logmel_ref(y, dtype=np.float32, **cfg)
+    evaluation of the same definition (ref_fn) makes against fp64 on this input."""
+    ref = ref_fn(y, **cfg)
+    f32 = ref_fn(y, dtype=np.float32, **cfg)
     return ref, factor * float(np.abs(f32.astype(np.float64) - ref).max())

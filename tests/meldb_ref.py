@@ -19,11 +19,7 @@ TOP_DB = 80.0
 
 def mag_ref(z, sr=16000, nfft=512, window=0.025, hop=0.01, dtype=np.float64):
     """|STFT| [n_frames, nfft//2 + 1] in `dtype`."""
-    win, hop_n, _ = R.sizes(sr, nfft, window, hop)
-    fr = R.frames_of(np.asarray(z, dtype=np.float64), nfft, win, hop_n).astype(dtype)
-    c, s = R.dft_basis(nfft, win)
-    re = fr @ c.astype(dtype)
-    im = fr @ s.astype(dtype)
+    re, im = R.spectrum_ref(z, sr, nfft, window, hop, dtype)
     return np.sqrt(re * re + im * im)
 
 
@@ -67,9 +63,5 @@ def fixed_ref(y, L, trim_top_db=60, dtype=np.float64, **kw):
 
 
 def err_bound(z, factor=6.0, **kw):
-    """(reference fp64 [n_frames, nmels], bound): bound = factor x the largest error the fp32 CPU
-    evaluation of the same definition makes against fp64 on this input (the yardstick of
-    logmel_ref.err_bound)."""
-    ref = meldb_ref(z, **kw)
-    f32 = meldb_ref(z, dtype=np.float32, **kw)
-    return ref, factor * float(np.abs(f32.astype(np.float64) - ref).max())
+    """logmel_ref.err_bound with meldb_ref as the definition."""
+    return R.err_bound(z, factor, meldb_ref, **kw)

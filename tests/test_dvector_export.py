@@ -73,7 +73,12 @@ def test_window_starts_matches_window_index(T):
     frame_off = [0, T, T + 7, 2 * T + 7, 2 * T + 107]
     starts, counts = dvector.window_starts(frame_off)
     assert starts.dtype == np.int32
-    assert np.array_equal(starts, dvector.window_index(frame_off)[:, 0])
+    # the literal loop of dvector_create.py:49-50 (window_index is built on window_starts now)
+    want = [a + j for a, b in zip(frame_off[:-1], frame_off[1:]) for j in range(0, b - a, dvector.HOP)
+            if j + dvector.WIN < b - a]
+    assert np.array_equal(starts, np.asarray(want, dtype=np.int64))
+    idx = dvector.window_index(frame_off)
+    assert idx.dtype == np.int64 and np.array_equal(idx, np.asarray(want)[:, None] + np.arange(dvector.WIN)[None, :])
     for (a, b), c in zip(zip(frame_off[:-1], frame_off[1:]), counts):
         assert c == dvector.window_frames(np.zeros((40, b - a), dtype=np.float32)).shape[0]
     assert sum(counts) == len(starts)

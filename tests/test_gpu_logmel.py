@@ -110,6 +110,12 @@ def test_device_resident_input_gives_the_same_bits():
     assert foff == foff2 and torch.equal(host, devi)
     one = features.logmel(torch.from_numpy(segs[0]).cuda())[0]
     assert torch.equal(one, host[:foff[1]])
+    # a lone slice of a larger device tensor, 4 bytes off the allocation's alignment: packed (copied)
+    # like every other input instead of being refused with SV_EALIGN
+    x_host = _signal("tones", 1235)
+    x_dev = torch.from_numpy(x_host).cuda()
+    assert x_dev[1:1235].data_ptr() % 16 == 4
+    assert torch.equal(features.logmel(x_dev[1:1235])[0], features.logmel(x_host[1:1235])[0])
 
 
 def _small_net():
