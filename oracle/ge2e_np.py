@@ -9,8 +9,10 @@ Follows the reference:
   calc_loss                utils.py:126-132  per = log(sum_k exp S + 1e-6) - S_jij, loss = sum
 
 Cosine as torch computes it: sum_d (x/max(|x|,1e-8)) * (y/max(|y|,1e-8))  (SURVEY §3.3).
-The backward is the closed form of SURVEY §8 a-G, differentiated by hand (the
-oracle is pinned by the reference's autograd through the golden dE/dw/db).
+The backward is the closed form of SURVEY §8 a-G, differentiated by hand.  It is pinned twice: by
+the reference's autograd through the golden dE/dw/db (unit-norm embeddings, where every 1/|x|
+factor and norm Jacobian is invisible), and off the unit sphere by fp64 autograd of the torch port
+on row norms from 0.05 to 20 (tests/test_ge2e_cases.py, inputs of tests/ge2e_cases.py).
 """
 from __future__ import annotations
 
@@ -152,7 +154,7 @@ class NumpyShardKernels:
         per = lz - np.stack([S[j, :, s0 + j] for j in range(Nl)])
         st = dict(E=E, Eh=Eh, En=En, Ch=Ch, Cn=Cn, Uh=Uh, Un=Un, raw=raw, rawd=rawd, lz=lz, s0=s0, N=N,
                   S=S)
-        return torch.tensor(per.sum()), torch.tensor(per), st
+        return torch.tensor(per.sum(), dtype=torch.float64), torch.tensor(per), st
 
     def bwd_rows(self, st, w, b, gloss):
         import torch
@@ -180,7 +182,7 @@ class NumpyShardKernels:
         red = np.zeros(Np * D + N)
         red[:N * D] = dchat.reshape(-1)
         red[Np * D:] = beta
-        return torch.tensor(red), torch.tensor([dw, db])
+        return torch.tensor(red), torch.tensor([dw, db], dtype=torch.float64)
 
     def finalize(self, st, red):
         import torch

@@ -28,8 +28,9 @@ class SpeechEmbedderPort(nn.Module):
         return x / torch.norm(x, dim=1).unsqueeze(1)
 
 
-def ge2e_loss(E, w, b):
-    """GE2ELoss.forward restated: centroids, leave-one-out diagonal, w*cos+b, sum loss."""
+def ge2e_per(E, w, b):
+    """GE2ELoss.forward restated up to calc_loss's per-embedding values [N, M]: centroids,
+    leave-one-out diagonal, w*cos+b, log-sum-exp minus the own-speaker entry."""
     N, M, D = E.shape
     C = E.mean(dim=1)
     U = (E.sum(dim=1, keepdim=True) - E) / (M - 1)
@@ -43,7 +44,12 @@ def ge2e_loss(E, w, b):
     S = w * cos + b
     pos = (S * eye).sum(-1)
     neg = torch.log(torch.exp(S).sum(-1) + 1e-6)
-    return (neg - pos).sum()
+    return neg - pos
+
+
+def ge2e_loss(E, w, b):
+    """GE2ELoss.forward restated: the sum of ge2e_per."""
+    return ge2e_per(E, w, b).sum()
 
 
 def load_recipe_weights(net, sd_np):

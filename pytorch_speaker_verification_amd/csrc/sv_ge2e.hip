@@ -177,13 +177,20 @@ __global__ __launch_bounds__(256) void ge2e_rowloss_kernel(float* __restrict__ c
   }
 }
 
-// fixed-order sum of n floats into out[0] (single block of 256)
+// fixed-order sum of n floats into out[0] (single block of 256), accumulated in fp64 and rounded
+// once: the loss.  Off the unit sphere the per-row losses reach 20 and their sum several thousand,
+// where an fp32 running sum loses up to an ulp of the total (2.4e-4 at 2048) and the fused and the
+// split path, which add in different orders, landed on neighbouring floats; every loss sum of
+// this file (here, ge2e_cols_kernel, ge2e_cols_partial_kernel) is now the rounding of the exact
+// sum of its per-row values.
 __global__ __launch_bounds__(256) void sum_kernel(const float* __restrict__ x, int n, float* __restrict__ out) {
-  __shared__ float red[4];
-  float s = 0.f;
-  for (int i = threadIdx.x; i < n; i += 256) s += x[i];
-  s = block_sum256(s, red);
-  if (threadIdx.x == 0) out[0] = s;
+  __shared__ double red[4];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) s += (double)x[i];
+  s = wave_sum_d(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) out[0] = (float)(((red[0] + red[1]) + red[2]) + red[3]);
 }
 
 // ---------------------------------------------------------------------------
@@ -1077,12 +1084,10 @@ static void launch_rows(int Bl, int M, int N, int D, int Np, int s0, const Ge2eW
 // 4 consecutive d (16-B loads), s one of 4 row sub-groups, so a wave's batch of GF_COLU loads
 // spans 4 GF_COLU rows and the whole c2 batch (640 rows) is one round trip to L2; rows in a fixed
 // order per (wave, sub-group), the sub-groups then the waves added in a fixed order.
-// PARTIAL (sharded form): k runs over all N speakers, the rows are this shard's; beta_k and dC^_k
-// (before the norm Jacobian) go to the reduce buffer [Np][D] + [N] for the all-reduce, and the
-// shard's dE is formed after it (ge2e_finalize_kernel); loss / dw / db are this shard's sums.
+// (The sharded form, where beta_k and dC^_k go to the reduce buffer for the all-reduce and dE is
+// formed after it, is ge2e_cols_partial_kernel + ge2e_finalize_kernel.)
 #define GF_COLW 16
 #define GF_COLU 10
-template <bool PARTIAL>
 __global__ __launch_bounds__(64 * GF_COLW) void ge2e_cols_kernel(int Bl, int M, int N, int D, int ldc,
                                                         const float* __restrict__ Chat, const float* __restrict__ Cn,
                                                         const float* __restrict__ Ehat, const float* __restrict__ Uhat,
@@ -1092,14 +1097,14 @@ __global__ __launch_bounds__(64 * GF_COLW) void ge2e_cols_kernel(int Bl, int M, 
                                                         const float* __restrict__ alpha, const float* __restrict__ dcd,
                                                         const float* __restrict__ G1, const float* __restrict__ per,
                                                         const float* __restrict__ dwdb_rows, float* __restrict__ dE,
-                                                        float* __restrict__ loss, float* __restrict__ dwdb,
-                                                        float* __restrict__ red_dchat, float* __restrict__ red_beta) {
+                                                        float* __restrict__ loss, float* __restrict__ dwdb) {
   constexpr int NW = GF_COLW, U = GF_COLU;
   __shared__ __attribute__((aligned(16))) float part[NW][64];
   __shared__ float bpart[NW];
   __shared__ float dCs[64];
   __shared__ float dUs[GF_MMAX][64];
-  __shared__ float red3[3][NW];
+  __shared__ float red2[2][NW];
+  __shared__ double redl[NW];
   const int k = blockIdx.x, q = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int s = lane >> 4, t = lane & 15;
@@ -1137,21 +1142,6 @@ __global__ __launch_bounds__(64 * GF_COLW) void ge2e_cols_kernel(int Bl, int M, 
   }
   if (lane < 16) *reinterpret_cast<float4*>(&part[w][4 * t]) = acc;
   if (lane == 0) bpart[w] = bsum;
-  if constexpr (PARTIAL) {
-    __syncthreads();
-    if (tid < 64 && q * 64 + tid < D) {
-      float dch = 0.f;
-#pragma unroll
-      for (int i = 0; i < NW; ++i) dch += part[i][tid];
-      red_dchat[(long)k * D + q * 64 + tid] = dch;
-    }
-    if (tid == 0 && q == 0) {
-      float beta = 0.f;
-#pragma unroll
-      for (int i = 0; i < NW; ++i) beta += bpart[i];
-      red_beta[k] = beta;
-    }
-  } else {
   // this wave's dE row (speaker k's utterance w): operands loaded before the barrier, dU shared
   // through LDS so the sum over the speaker's M rows needs no second trip to memory
   const int d = q * 64 + lane;
@@ -1192,31 +1182,32 @@ __global__ __launch_bounds__(64 * GF_COLW) void ge2e_cols_kernel(int Bl, int M, 
     for (int i = 0; i < M; ++i) sumdU += dUs[i][lane];
     dE[rdx] = gE + dCs[lane] * invM + (sumdU - dU) * invm1;
   }
-  }  // !PARTIAL
   if (k == 0 && q == 0) {  // loss = sum per, dw, db: fixed-order block sums (block-uniform branch)
-    float l = 0.f, a = 0.f, b = 0.f;
+    double l = 0.0;  // the loss in fp64, rounded once (sum_kernel)
+    float a = 0.f, b = 0.f;
     for (int i = tid; i < Bl; i += 64 * NW) {
-      l += per[i];
+      l += (double)per[i];
       a += dwdb_rows[i];
       b += dwdb_rows[Bl + i];
     }
-    l = wave_sum(l);
+    l = wave_sum_d(l);
     a = wave_sum(a);
     b = wave_sum(b);
     if (lane == 0) {
-      red3[0][w] = l;
-      red3[1][w] = a;
-      red3[2][w] = b;
+      redl[w] = l;
+      red2[0][w] = a;
+      red2[1][w] = b;
     }
     __syncthreads();
     if (tid == 0) {
-      float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+      double s0 = 0.0;
+      float s1 = 0.f, s2 = 0.f;
       for (int i = 0; i < NW; ++i) {
-        s0 += red3[0][i];
-        s1 += red3[1][i];
-        s2 += red3[2][i];
+        s0 += redl[i];
+        s1 += red2[0][i];
+        s2 += red2[1][i];
       }
-      loss[0] = s0;
+      loss[0] = (float)s0;
       dwdb[0] = s1;
       dwdb[1] = s2;
     }
@@ -1230,8 +1221,8 @@ __global__ __launch_bounds__(64 * GF_COLW) void ge2e_cols_kernel(int Bl, int M, 
 // in LDS in wave order -- every speaker's sums in the same order for any KB.  Writes this shard's
 // dC^_k and beta_k to the reduce buffer, and workgroup 0 the shard's loss / dw / db partials
 // (r05: KB = 1 ran 256 workgroups that each streamed all of E^ from L2, 84 MB at c5's rank shape,
-// 7.5-9.4 us; ge2e_cols_kernel<true> before it ran (N, D / 64) workgroups, 11 us; KB = 2 / 4 with
-// 16-B broadcast loads measured 10.2 / 11.8 us: the product launches KB = 1).
+// 7.5-9.4 us; a sharded variant of ge2e_cols_kernel, since removed, ran (N, D / 64) workgroups,
+// 11 us; KB = 2 / 4 with 16-B broadcast loads measured 10.2 / 11.8 us: the product launches KB = 1).
 template <int KB>
 __global__ __launch_bounds__(1024) void ge2e_cols_partial_kernel(int Bl, int N, int D, int ldc,
                                                                  const float* __restrict__ Ehat,
@@ -1245,7 +1236,8 @@ __global__ __launch_bounds__(1024) void ge2e_cols_partial_kernel(int Bl, int N, 
   constexpr int NW = 16;
   __shared__ __attribute__((aligned(16))) float4 part[KB][NW][64];
   __shared__ float bpart[KB][NW];
-  __shared__ float red3[3][NW];
+  __shared__ float red2[2][NW];
+  __shared__ double redl[NW];
   const int k0 = blockIdx.x * KB, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const bool dok = 4 * lane < D;
   float4 acc[KB];
@@ -1310,29 +1302,31 @@ __global__ __launch_bounds__(1024) void ge2e_cols_partial_kernel(int Bl, int N, 
   }
   const int k = blockIdx.x;
   if (k == 0) {  // loss = sum per, dw, db: fixed-order block sums (block-uniform branch)
-    float l = 0.f, a = 0.f, b = 0.f;
+    double l = 0.0;  // the loss in fp64, rounded once (sum_kernel)
+    float a = 0.f, b = 0.f;
     for (int i = tid; i < Bl; i += 64 * NW) {
-      l += per[i];
+      l += (double)per[i];
       a += dwdb_rows[i];
       b += dwdb_rows[Bl + i];
     }
-    l = wave_sum(l);
+    l = wave_sum_d(l);
     a = wave_sum(a);
     b = wave_sum(b);
     if (lane == 0) {
-      red3[0][w] = l;
-      red3[1][w] = a;
-      red3[2][w] = b;
+      redl[w] = l;
+      red2[0][w] = a;
+      red2[1][w] = b;
     }
     __syncthreads();
     if (tid == 0) {
-      float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+      double s0 = 0.0;
+      float s1 = 0.f, s2 = 0.f;
       for (int i = 0; i < NW; ++i) {
-        s0 += red3[0][i];
-        s1 += red3[1][i];
-        s2 += red3[2][i];
+        s0 += redl[i];
+        s1 += red2[0][i];
+        s2 += red2[1][i];
       }
-      loss[0] = s0;
+      loss[0] = (float)s0;
       dwdb[0] = s1;
       dwdb[1] = s2;
     }
@@ -1358,9 +1352,9 @@ extern "C" int sv_ge2e_train(const float* E, int N, int M, int D, const float* w
   SV_LAUNCH_CHECK();
   launch_rows(Bl, M, N, D, Np, 0, ws, w, b, per, stream);
   SV_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ge2e_cols_kernel<false>, dim3(N, (D + 63) / 64), dim3(64 * GF_COLW), 0, stream, Bl, M, N, D, Np, ws.Chat, ws.Cn,
+  hipLaunchKernelGGL(ge2e_cols_kernel, dim3(N, (D + 63) / 64), dim3(64 * GF_COLW), 0, stream, Bl, M, N, D, Np, ws.Chat, ws.Cn,
                      ws.Ehat, ws.Uhat, ws.En, ws.Un, ws.rawd, ws.cos, ws.dcos, ws.alpha, ws.dcd, ws.G1, per,
-                     ws.dwdb_rows, dE, loss, dwdb, nullptr, nullptr);
+                     ws.dwdb_rows, dE, loss, dwdb);
   SV_LAUNCH_CHECK();
   return SV_OK;
 }
@@ -1405,14 +1399,9 @@ extern "C" int sv_ge2e_shard_rows(int N_local, int M, int D, int spk_offset, int
     hipError_t e = sv_memset0(red + (size_t)N * D, (size_t)(Np - N) * D * sizeof(float), stream);
     if (e != hipSuccess) return (int)e;
   }
-  if (D <= 256)
-    hipLaunchKernelGGL(ge2e_cols_partial_kernel<1>, dim3(N),
-                       dim3(1024), 0, stream, Bl, N, D, Np, ws.Ehat, ws.cos, ws.dcos, per, ws.dwdb_rows, loss_local,
-                       dwdb_local, red, red + (size_t)Np * D);
-  else
-    hipLaunchKernelGGL(ge2e_cols_kernel<true>, dim3(N, (D + 63) / 64), dim3(64 * GF_COLW), 0, stream, Bl, M, N, D, Np,
-                       ws.Chat, ws.Cn, ws.Ehat, ws.Uhat, ws.En, ws.Un, ws.rawd, ws.cos, ws.dcos, ws.alpha, ws.dcd,
-                       ws.G1, per, ws.dwdb_rows, nullptr, loss_local, dwdb_local, red, red + (size_t)Np * D);
+  // (D <= GF_DMAX = 256 by sv_ge2e_train_ok above: one lane per 4 d covers a row)
+  hipLaunchKernelGGL(ge2e_cols_partial_kernel<1>, dim3(N), dim3(1024), 0, stream, Bl, N, D, Np, ws.Ehat, ws.cos, ws.dcos,
+                     per, ws.dwdb_rows, loss_local, dwdb_local, red, red + (size_t)Np * D);
   SV_LAUNCH_CHECK();
   return SV_OK;
 }
