@@ -6,7 +6,7 @@ out of scope and raises only when called: there is no audio deco
 ``mel_db`` on decoded audio is ``pytorch_speaker_verification_amd.features.mel_db_fixed``
 (``data_load.SpeakerDatasetWaveforms`` serves it).
 """
-from pytorch_speaker_verification_amd.utils import calc_loss, get_centroids, get_cossim  # noqa: F401
+from pytorch_speaker_verification_amd.utils import calc_loss, calc_loss_contrast, get_centroids, get_cossim  # noqa: F401
 
 
 def mfccs_and_spec(wav_file, wav_process=False, calc_mfccs=False, calc_mag_db=False):

@@ -245,6 +245,45 @@ int sv_ge2e_calc_loss_bwd(const float* S, int N, int M, int K, const float* glos
 int sv_eer_counts(const float* S, int N, int M2, int Nc, const float* thresholds, int n_thr, float* cnt_all,
                   float* cnt_diag, hipStream_t stream);
 
+/* ---- GE2E contrast loss (added under v12; additive): eq. 7 of the GE2E paper (arXiv 1710.10467, the
+ * text-dependent loss) beside the softmax loss (eq. 6) the entry points above compute.  On the same
+ * cos and S = w (cos + 1e-6) + b:
+ *   per[j,i] = 1 - sigma(S[j,i,j]) + max_{k != j} sigma(S[j,i,k]),   loss = sum per.
+ * The maximum is taken where S is largest over k != j (sigma is monotone: a negative w selects the
+ * smallest cosine), ties to the lowest k (torch.max(dim)'s index).  Row backward with p = sigma(S_jj),
+ * q = sigma(S_jk*): dS[j] = -p (1 - p), dS[k*] = q (1 - q), every other dS exactly 0, all scaled by the
+ * upstream gloss.  sigma is evaluated from e^{-|x|}, so it neither overflows nor loses the small tail.
+ * Each `_as` entry point is its namesake with a leading `loss` argument: SV_GE2E_SOFTMAX runs exactly
+ * the namesake (which forwards here), SV_GE2E_CONTRAST swaps the row step only -- the fused
+ * path's rows kernel (one kernel over the whole sv_ge2e_train_ok domain, local or sharded) or the
+ * split path's row-loss / row-backward / diagonal kernels; prep, centroids, GEMMs, the column step
+ * and finalize are shared, and so are the workspace (sv_ge2e_workspace_size; the split forward keeps
+ * each row's k* in it for the backward), sv_ge2e_speaker_sums, sv_ge2e_bwd_finalize,
+ * sv_ge2e_shard_prep and sv_ge2e_shard_finalize.  An unknown `loss` is SV_EARG and the contrast loss
+ * with N < 2 speakers (no negative) SV_ESHAPE, both before any launch. */
+enum sv_ge2e_loss_kind { SV_GE2E_SOFTMAX = 0, SV_GE2E_CONTRAST = 1 };
+int sv_ge2e_fwd_rows_as(int loss, const float* E, int N_local, int M, int D, int spk_offset, int N,
+                        const float* ssum_all, const float* w, const float* b, float* per, float* loss_local,
+                        float* workspace, hipStream_t stream);
+int sv_ge2e_fwd_as(int loss_kind, const float* E, int N, int M, int D, const float* w, const float* b, float* loss,
+                   float* per, float* workspace, float* ssum, hipStream_t stream);
+int sv_ge2e_bwd_rows_as(int loss, int N_local, int M, int D, int spk_offset, int N, const float* w, const float* b,
+                        const float* gloss, float* dchat_partial, float* beta_partial, float* dwdb, float* workspace,
+                        hipStream_t stream);
+int sv_ge2e_bwd_as(int loss, int N, int M, int D, const float* w, const float* b, const float* gloss, float* dE,
+                   float* dwdb, float* dchat, float* beta, float* workspace, hipStream_t stream);
+int sv_ge2e_train_as(int loss_kind, const float* E, int N, int M, int D, const float* w, const float* b, float* loss,
+                     float* per, float* dE, float* dwdb, float* workspace, hipStream_t stream);
+int sv_ge2e_shard_rows_as(int loss, int N_local, int M, int D, int spk_offset, int N, const float* ssum_all,
+                          const float* w, const float* b, float* per, float* red, float* loss_local, float* dwdb_local,
+                          float* workspace, hipStream_t stream);
+/* the contrast loss on a given S [N,M,K], K >= N and K >= 2 (else SV_ESHAPE): the positive is column
+ * j, the maximum runs over every k != j, k < K; mirrors sv_ge2e_calc_loss / _bwd:
+ * dS from gloss (device scalar, NULL = 0) and gper [N,M] (NULL = 0). */
+int sv_ge2e_calc_contrast(const float* S, int N, int M, int K, float* per, float* loss, hipStream_t stream);
+int sv_ge2e_calc_contrast_bwd(const float* S, int N, int M, int K, const float* gloss, const float* gper, float* dS,
+                              hipStream_t stream);
+
 /* ---- bf16 mixed-precision variant (BASELINE config c3) ---------------------------------------
  * GEMM operands (weights, h, dgates) in bf16 (RNE casts), bf16 MFMA with fp32 accumulation;
  * the stored x-projection (K1 output incl. biases) and the saved activated gates are bf16 (ABI

@@ -18,6 +18,16 @@ LIB_PATH = os.path.join(_HERE, "libsv_ge2e.so")
 FAULT_LIB_PATH = os.path.join(_HERE, "libsv_ge2e_faultinj.so")
 ABI_VERSION = 12
 SV_DTYPE_F32, SV_DTYPE_BF16 = 0, 1  # include/sv_ge2e.h
+# the GE2E loss of the `_as` entry points (include/sv_ge2e.h enum sv_ge2e_loss_kind), by name
+LOSS_METHODS = {"softmax": 0, "contrast": 1}
+
+
+def loss_id(loss_method):
+    """'softmax' | 'contrast' -> SV_GE2E_SOFTMAX / SV_GE2E_CONTRAST."""
+    try:
+        return LOSS_METHODS[loss_method]
+    except (KeyError, TypeError):
+        raise ValueError(f"unknown loss_method {loss_method!r} (expected one of {sorted(LOSS_METHODS)})") from None
 
 # schedule flags of the bf16 stack (include/sv_ge2e.h SV_SCHED_*), by name
 SCHEDULES = {"auto": 0, "per_layer": 1, "per_step": 2, "persist": 5}  # persist: per-layer persistent, any H
@@ -91,6 +101,16 @@ SIGNATURES = {
     "sv_ge2e_cossim_bwd_workspace": (_c_size_t, [_c_int, _c_int, _c_int, _c_int]),
     "sv_ge2e_cossim_bwd": (_c_int, [_P, _c_int, _c_int, _c_int, _P, _c_int, _P, _P, _P, _P, _P]),
     "sv_ge2e_calc_loss_bwd": (_c_int, [_P, _c_int, _c_int, _c_int, _P, _P, _P, _P]),
+    # the loss-kind forms (SV_GE2E_SOFTMAX / SV_GE2E_CONTRAST): their namesakes with a leading int
+    "sv_ge2e_fwd_rows_as": (_c_int, [_c_int, _P, _c_int, _c_int, _c_int, _c_int, _c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "sv_ge2e_fwd_as": (_c_int, [_c_int, _P, _c_int, _c_int, _c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "sv_ge2e_bwd_rows_as": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "sv_ge2e_bwd_as": (_c_int, [_c_int, _c_int, _c_int, _c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "sv_ge2e_train_as": (_c_int, [_c_int, _P, _c_int, _c_int, _c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "sv_ge2e_shard_rows_as": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _P, _P, _P, _P, _P, _P, _P, _P,
+                                       _P]),
+    "sv_ge2e_calc_contrast": (_c_int, [_P, _c_int, _c_int, _c_int, _P, _P, _P]),
+    "sv_ge2e_calc_contrast_bwd": (_c_int, [_P, _c_int, _c_int, _c_int, _P, _P, _P, _P]),
     "sv_gemm_bf16_workspace": (_c_size_t, [_c_int, _c_int, _c_int]),
     "sv_gemm_bf16": (_c_int, [_c_int, _c_int, _c_int, _P, _c_long, _P, _c_long, _P, _c_long, _P, _P, _c_float, _P,
                               _P]),
@@ -194,6 +214,15 @@ def call(name, *args):
     if rc != 0:
         msg = ERRORS.get(rc, f"HIP error {rc}")
         raise RuntimeError(f"{name} failed: {msg}")
+
+
+def call_as(name, kind, *args):
+    """``name`` for the softmax loss (kind 0: the entry point every caller had before the loss
+    argument), its ``_as`` sibling with the leading loss id otherwise (include/sv_ge2e.h)."""
+    if kind == 0:
+        call(name, *args)
+    else:
+        call(name + "_as", kind, *args)
 
 
 def ptr(t):

@@ -388,6 +388,12 @@ __global__ void ge2e_dcd_kernel(const float* __restrict__ rawd, const float* __r
   dcd[r] = w * g * (p - 1.0f);
 }
 
+#include "sv_ge2e_contrast.h"
+
+static bool loss_known(int loss) { return loss == SV_GE2E_SOFTMAX || loss == SV_GE2E_CONTRAST; }
+// the contrast loss needs a negative: at least two speakers in the (global) batch
+static bool loss_shape_ok(int loss, int N) { return loss != SV_GE2E_CONTRAST || N >= 2; }
+
 // ============================================================================
 // C ABI
 // ============================================================================
@@ -406,9 +412,11 @@ extern "C" int sv_ge2e_speaker_sums(const float* E, int N_local, int M, int D, f
   return SV_OK;
 }
 
-extern "C" int sv_ge2e_fwd_rows(const float* E, int N_local, int M, int D, int spk_offset, int N, const float* ssum_all,
-                                const float* w, const float* b, float* per, float* loss_local, float* workspace,
-                                hipStream_t stream) {
+extern "C" int sv_ge2e_fwd_rows_as(int loss, const float* E, int N_local, int M, int D, int spk_offset, int N,
+                                   const float* ssum_all, const float* w, const float* b, float* per, float* loss_local,
+                                   float* workspace, hipStream_t stream) {
+  if (!loss_known(loss)) return SV_EARG;
+  if (!loss_shape_ok(loss, N)) return SV_ESHAPE;
   if (!ge2e_args_ok(E, N_local, M, D, spk_offset, N) || !ssum_all || !w || !b || !per || !workspace) return SV_EARG;
   const Ge2eWs ws = carve(workspace, N_local, M, D, N);
   const int Bl = N_local * M, Np = (N + 3) & ~3;
@@ -420,8 +428,12 @@ extern "C" int sv_ge2e_fwd_rows(const float* E, int N_local, int M, int D, int s
   // cos = E^ C^T  (fp32 MFMA; rows of E^ and C^ are both D-contiguous)
   int rc = gemm_f32(1, 1, Bl, Np, D, ws.Ehat, D, ws.Chat, D, ws.cos, Np, nullptr, nullptr, 0.f, ws.gemm, stream);
   if (rc) return rc;
-  hipLaunchKernelGGL(ge2e_rowloss_kernel, dim3((Bl + 3) / 4), dim3(256), 0, stream, ws.cos, ws.rawd, Bl, M, N, Np,
-                     spk_offset, w, b, per, ws.logz);
+  if (loss == SV_GE2E_CONTRAST)  // (k* of every row goes to the logz slot)
+    hipLaunchKernelGGL(ge2e_rowloss_contrast_kernel, dim3((Bl + 3) / 4), dim3(256), 0, stream, ws.cos, ws.rawd, Bl, M, N,
+                       Np, spk_offset, w, b, per, ws.logz);
+  else
+    hipLaunchKernelGGL(ge2e_rowloss_kernel, dim3((Bl + 3) / 4), dim3(256), 0, stream, ws.cos, ws.rawd, Bl, M, N, Np,
+                       spk_offset, w, b, per, ws.logz);
   SV_LAUNCH_CHECK();
   if (loss_local) {
     hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(256), 0, stream, per, Bl, loss_local);
@@ -430,24 +442,44 @@ extern "C" int sv_ge2e_fwd_rows(const float* E, int N_local, int M, int D, int s
   return SV_OK;
 }
 
-extern "C" int sv_ge2e_fwd(const float* E, int N, int M, int D, const float* w, const float* b, float* loss, float* per,
-                           float* workspace, float* ssum, hipStream_t stream) {
+extern "C" int sv_ge2e_fwd_rows(const float* E, int N_local, int M, int D, int spk_offset, int N, const float* ssum_all,
+                                const float* w, const float* b, float* per, float* loss_local, float* workspace,
+                                hipStream_t stream) {
+  return sv_ge2e_fwd_rows_as(SV_GE2E_SOFTMAX, E, N_local, M, D, spk_offset, N, ssum_all, w, b, per, loss_local, workspace,
+                             stream);
+}
+
+extern "C" int sv_ge2e_fwd_as(int loss_kind, const float* E, int N, int M, int D, const float* w, const float* b,
+                              float* loss, float* per, float* workspace, float* ssum, hipStream_t stream) {
+  if (!loss_known(loss_kind)) return SV_EARG;
+  if (!loss_shape_ok(loss_kind, N)) return SV_ESHAPE;
   if (!ssum) return SV_EARG;
   int rc = sv_ge2e_speaker_sums(E, N, M, D, ssum, stream);
   if (rc) return rc;
-  return sv_ge2e_fwd_rows(E, N, M, D, 0, N, ssum, w, b, per, loss, workspace, stream);
+  return sv_ge2e_fwd_rows_as(loss_kind, E, N, M, D, 0, N, ssum, w, b, per, loss, workspace, stream);
 }
 
-extern "C" int sv_ge2e_bwd_rows(int N_local, int M, int D, int spk_offset, int N, const float* w, const float* b,
-                                const float* gloss, float* dchat_partial, float* beta_partial, float* dwdb,
-                                float* workspace, hipStream_t stream) {
+extern "C" int sv_ge2e_fwd(const float* E, int N, int M, int D, const float* w, const float* b, float* loss, float* per,
+                           float* workspace, float* ssum, hipStream_t stream) {
+  return sv_ge2e_fwd_as(SV_GE2E_SOFTMAX, E, N, M, D, w, b, loss, per, workspace, ssum, stream);
+}
+
+extern "C" int sv_ge2e_bwd_rows_as(int loss, int N_local, int M, int D, int spk_offset, int N, const float* w,
+                                   const float* b, const float* gloss, float* dchat_partial, float* beta_partial,
+                                   float* dwdb, float* workspace, hipStream_t stream) {
+  if (!loss_known(loss)) return SV_EARG;
+  if (!loss_shape_ok(loss, N)) return SV_ESHAPE;
   if (N_local <= 0 || M < 2 || D <= 0 || N < N_local || !w || !b || !dchat_partial || !beta_partial || !dwdb ||
       !workspace)
     return SV_EARG;
   const Ge2eWs ws = carve(workspace, N_local, M, D, N);
   const int Bl = N_local * M, Np = (N + 3) & ~3;
-  hipLaunchKernelGGL(ge2e_rowbwd_kernel, dim3((Bl + 3) / 4), dim3(256), 0, stream, ws.cos, ws.logz, Bl, M, N, Np,
-                     spk_offset, w, b, gloss, ws.dcos, ws.alpha, ws.dwdb_rows);
+  if (loss == SV_GE2E_CONTRAST)
+    hipLaunchKernelGGL(ge2e_rowbwd_contrast_kernel, dim3((Bl + 3) / 4), dim3(256), 0, stream, ws.cos, ws.logz, Bl, M, N, Np,
+                       spk_offset, w, b, gloss, ws.dcos, ws.alpha, ws.dwdb_rows);
+  else
+    hipLaunchKernelGGL(ge2e_rowbwd_kernel, dim3((Bl + 3) / 4), dim3(256), 0, stream, ws.cos, ws.logz, Bl, M, N, Np,
+                       spk_offset, w, b, gloss, ws.dcos, ws.alpha, ws.dwdb_rows);
   SV_LAUNCH_CHECK();
   // G1 = dcos_off C^   ([Bl, N] x [N, D]; C^ read as [K=N][D] row-contiguous)
   int rc = gemm_f32(1, 0, Bl, D, Np, ws.dcos, Np, ws.Chat, D, ws.G1, D, nullptr, nullptr, 0.f, ws.gemm, stream);
@@ -465,10 +497,21 @@ extern "C" int sv_ge2e_bwd_rows(int N_local, int M, int D, int spk_offset, int N
   hipLaunchKernelGGL(ge2e_dwdb_kernel, dim3(1), dim3(256), 0, stream, ws.dwdb_rows, Bl, dwdb);
   SV_LAUNCH_CHECK();
   // diagonal dcos into the (now free) dwdb_rows slot for the finalize step
-  hipLaunchKernelGGL(ge2e_dcd_kernel, dim3((Bl + 255) / 256), dim3(256), 0, stream, ws.rawd, ws.logz, Bl, w, b, gloss,
-                     ws.dwdb_rows);
+  if (loss == SV_GE2E_CONTRAST)
+    hipLaunchKernelGGL(ge2e_dcd_contrast_kernel, dim3((Bl + 255) / 256), dim3(256), 0, stream, ws.rawd, Bl, w, b, gloss,
+                       ws.dwdb_rows);
+  else
+    hipLaunchKernelGGL(ge2e_dcd_kernel, dim3((Bl + 255) / 256), dim3(256), 0, stream, ws.rawd, ws.logz, Bl, w, b, gloss,
+                       ws.dwdb_rows);
   SV_LAUNCH_CHECK();
   return SV_OK;
+}
+
+extern "C" int sv_ge2e_bwd_rows(int N_local, int M, int D, int spk_offset, int N, const float* w, const float* b,
+                                const float* gloss, float* dchat_partial, float* beta_partial, float* dwdb,
+                                float* workspace, hipStream_t stream) {
+  return sv_ge2e_bwd_rows_as(SV_GE2E_SOFTMAX, N_local, M, D, spk_offset, N, w, b, gloss, dchat_partial, beta_partial, dwdb,
+                             workspace, stream);
 }
 
 extern "C" int sv_ge2e_bwd_finalize(int N_local, int M, int D, int spk_offset, int N, const float* dchat,
@@ -480,11 +523,16 @@ extern "C" int sv_ge2e_bwd_finalize(int N_local, int M, int D, int spk_offset, i
   return SV_OK;
 }
 
-extern "C" int sv_ge2e_bwd(int N, int M, int D, const float* w, const float* b, const float* gloss, float* dE,
-                           float* dwdb, float* dchat, float* beta, float* workspace, hipStream_t stream) {
-  int rc = sv_ge2e_bwd_rows(N, M, D, 0, N, w, b, gloss, dchat, beta, dwdb, workspace, stream);
+extern "C" int sv_ge2e_bwd_as(int loss, int N, int M, int D, const float* w, const float* b, const float* gloss,
+                              float* dE, float* dwdb, float* dchat, float* beta, float* workspace, hipStream_t stream) {
+  int rc = sv_ge2e_bwd_rows_as(loss, N, M, D, 0, N, w, b, gloss, dchat, beta, dwdb, workspace, stream);
   if (rc) return rc;
   return sv_ge2e_bwd_finalize(N, M, D, 0, N, dchat, beta, dE, workspace, stream);
+}
+
+extern "C" int sv_ge2e_bwd(int N, int M, int D, const float* w, const float* b, const float* gloss, float* dE,
+                           float* dwdb, float* dchat, float* beta, float* workspace, hipStream_t stream) {
+  return sv_ge2e_bwd_as(SV_GE2E_SOFTMAX, N, M, D, w, b, gloss, dE, dwdb, dchat, beta, workspace, stream);
 }
 
 // ============================================================================
@@ -1050,12 +1098,36 @@ __global__ __launch_bounds__(64 * NWV) void ge2e_rows4r_kernel(const float* __re
   }
 }
 
+// rows per workgroup of ge2e_rows_contrast_kernel above CT_TILE speakers: the fewest of 4 / 8 / 16 that
+// put the Bl rows on the device in one round of workgroups (one per CU: the tile fills the LDS), 16
+// beyond that
+static int ct_rows_per_wg(int Bl, int cus) {
+  for (int rw = CT_ROWW; rw < 16; rw *= 2)
+    if ((Bl + rw - 1) / rw <= cus) return rw;
+  return 16;
+}
+
 // launch F2 for N speakers (<= GF_NMAX)
 // (ssum != nullptr: the sharded form's all-gathered sums -- at 128 < N <= 256, D = 256 the rows
 // kernel forms C^ itself, rows_fuse_centroids; else the caller runs ge2e_centroid_kernel first)
 static bool rows_fuse_centroids(int N, int D) { return N > GF_TILE && N <= GF_NMAX && D == 256; }
 static void launch_rows(int Bl, int M, int N, int D, int Np, int s0, const Ge2eWs& ws, const float* w, const float* b,
-                        float* per, hipStream_t stream, const float* ssum = nullptr) {
+                        float* per, hipStream_t stream, const float* ssum = nullptr, int loss = SV_GE2E_SOFTMAX) {
+  if (loss == SV_GE2E_CONTRAST) {  // one kernel for every fused shape; C^ always from ws.Chat
+    const int NT = N <= CT_TILE ? N : CT_TILE;
+    const int RW = N <= CT_TILE ? CT_ROWW : ct_rows_per_wg(Bl, sv_stream_cus(stream));
+    const size_t lds = ((size_t)NT * (D + 4) + RW * (size_t)D) * sizeof(float);
+    const dim3 grid((Bl + RW - 1) / RW), block(64 * RW);
+#define CT_LAUNCH(NH, RWV)                                                                                             \
+  hipLaunchKernelGGL((ge2e_rows_contrast_kernel<NH, RWV>), grid, block, lds, stream, ws.Chat, ws.Ehat, ws.rawd, Bl, M, N, D, \
+                     Np, s0, w, b, per, ws.cos, ws.dcos, ws.alpha, ws.dcd, ws.dwdb_rows, ws.G1)
+    if (N <= CT_TILE) CT_LAUNCH(2, CT_ROWW);
+    else if (RW == 4) CT_LAUNCH(4, 4);
+    else if (RW == 8) CT_LAUNCH(4, 8);
+    else CT_LAUNCH(4, 16);
+#undef CT_LAUNCH
+    return;
+  }
   if (N > GF_TILE && D == 256) {
     const size_t lds = ((size_t)GF_CH * GF_R4LDC + 4 * GF_NMAX + 4 * GF_CH + GF_CH + 32) * sizeof(float);
     constexpr int R4W = 8, R4R = 2;
@@ -1340,8 +1412,10 @@ extern "C" int sv_ge2e_train_ok(int N, int M, int D) {
 
 // fused forward + backward of GE2ELoss for one GPU holding all N speakers (gloss = 1, the
 // training step's): loss, per [N,M], dE [N,M,D], dwdb [2] = (dL/dw, dL/db)
-extern "C" int sv_ge2e_train(const float* E, int N, int M, int D, const float* w, const float* b, float* loss,
-                             float* per, float* dE, float* dwdb, float* workspace, hipStream_t stream) {
+extern "C" int sv_ge2e_train_as(int loss_kind, const float* E, int N, int M, int D, const float* w, const float* b,
+                                float* loss, float* per, float* dE, float* dwdb, float* workspace, hipStream_t stream) {
+  if (!loss_known(loss_kind)) return SV_EARG;
+  if (!loss_shape_ok(loss_kind, N)) return SV_ESHAPE;
   if (!E || !w || !b || !loss || !per || !dE || !dwdb || !workspace) return SV_EARG;
   if (!sv_ge2e_train_ok(N, M, D)) return SV_ESHAPE;
   if (((uintptr_t)E | (uintptr_t)workspace) & 15) return SV_EALIGN;
@@ -1350,13 +1424,18 @@ extern "C" int sv_ge2e_train(const float* E, int N, int M, int D, const float* w
   hipLaunchKernelGGL(ge2e_prep_kernel, dim3(N), dim3(256), 0, stream, E, M, D, ws.Chat, ws.Cn, ws.Ehat, ws.Uhat,
                      ws.En, ws.Un, ws.rawd, nullptr);
   SV_LAUNCH_CHECK();
-  launch_rows(Bl, M, N, D, Np, 0, ws, w, b, per, stream);
+  launch_rows(Bl, M, N, D, Np, 0, ws, w, b, per, stream, nullptr, loss_kind);
   SV_LAUNCH_CHECK();
   hipLaunchKernelGGL(ge2e_cols_kernel, dim3(N, (D + 63) / 64), dim3(64 * GF_COLW), 0, stream, Bl, M, N, D, Np, ws.Chat, ws.Cn,
                      ws.Ehat, ws.Uhat, ws.En, ws.Un, ws.rawd, ws.cos, ws.dcos, ws.alpha, ws.dcd, ws.G1, per,
                      ws.dwdb_rows, dE, loss, dwdb);
   SV_LAUNCH_CHECK();
   return SV_OK;
+}
+
+extern "C" int sv_ge2e_train(const float* E, int N, int M, int D, const float* w, const float* b, float* loss,
+                             float* per, float* dE, float* dwdb, float* workspace, hipStream_t stream) {
+  return sv_ge2e_train_as(SV_GE2E_SOFTMAX, E, N, M, D, w, b, loss, per, dE, dwdb, workspace, stream);
 }
 
 // ---- the fused kernels in the speaker-sharded form (data parallel, sharded_ge2e.py) ----
@@ -1379,19 +1458,21 @@ extern "C" int sv_ge2e_shard_prep(const float* E, int N_local, int M, int D, flo
   return SV_OK;
 }
 
-extern "C" int sv_ge2e_shard_rows(int N_local, int M, int D, int spk_offset, int N, const float* ssum_all,
-                                  const float* w, const float* b, float* per, float* red, float* loss_local,
-                                  float* dwdb_local, float* workspace, hipStream_t stream) {
+extern "C" int sv_ge2e_shard_rows_as(int loss, int N_local, int M, int D, int spk_offset, int N, const float* ssum_all,
+                                     const float* w, const float* b, float* per, float* red, float* loss_local,
+                                     float* dwdb_local, float* workspace, hipStream_t stream) {
+  if (!loss_known(loss)) return SV_EARG;
+  if (!loss_shape_ok(loss, N)) return SV_ESHAPE;
   if (!ssum_all || !w || !b || !per || !red || !loss_local || !dwdb_local || !workspace) return SV_EARG;
   if (!sv_ge2e_train_ok(N, M, D) || N_local <= 0 || spk_offset < 0 || spk_offset + N_local > N) return SV_ESHAPE;
   const Ge2eWs ws = carve(workspace, N_local, M, D, N);
   const int Bl = N_local * M, Np = (N + 3) & ~3;
-  if (rows_fuse_centroids(N, D) && Np == N) {  // (C^ formed inside the rows kernel)
+  if (loss == SV_GE2E_SOFTMAX && rows_fuse_centroids(N, D) && Np == N) {  // (C^ formed inside the rows kernel)
     launch_rows(Bl, M, N, D, Np, spk_offset, ws, w, b, per, stream, ssum_all);
   } else {
     hipLaunchKernelGGL(ge2e_centroid_kernel, dim3(Np), dim3(256), 0, stream, ssum_all, N, M, D, ws.Chat, ws.Cn);
     SV_LAUNCH_CHECK();
-    launch_rows(Bl, M, N, D, Np, spk_offset, ws, w, b, per, stream);
+    launch_rows(Bl, M, N, D, Np, spk_offset, ws, w, b, per, stream, nullptr, loss);
   }
   SV_LAUNCH_CHECK();
   // the padding rows of dC^ (speakers N .. Np-1) stay zero through the all-reduce
@@ -1404,6 +1485,13 @@ extern "C" int sv_ge2e_shard_rows(int N_local, int M, int D, int spk_offset, int
                      per, ws.dwdb_rows, loss_local, dwdb_local, red, red + (size_t)Np * D);
   SV_LAUNCH_CHECK();
   return SV_OK;
+}
+
+extern "C" int sv_ge2e_shard_rows(int N_local, int M, int D, int spk_offset, int N, const float* ssum_all,
+                                  const float* w, const float* b, float* per, float* red, float* loss_local,
+                                  float* dwdb_local, float* workspace, hipStream_t stream) {
+  return sv_ge2e_shard_rows_as(SV_GE2E_SOFTMAX, N_local, M, D, spk_offset, N, ssum_all, w, b, per, red, loss_local,
+                               dwdb_local, workspace, stream);
 }
 
 extern "C" int sv_ge2e_shard_finalize(int N_local, int M, int D, int spk_offset, int N, const float* red, float* dE,
@@ -1505,6 +1593,31 @@ extern "C" int sv_ge2e_calc_loss(const float* S, int N, int M, int K, float* per
     hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(256), 0, stream, per, Bl, loss);
     SV_LAUNCH_CHECK();
   }
+  return SV_OK;
+}
+
+// calc_loss's contrast counterpart on S [N, M, K] (K >= N, at least one k != j)
+extern "C" int sv_ge2e_calc_contrast(const float* S, int N, int M, int K, float* per, float* loss, hipStream_t stream) {
+  if (!S || !per || N <= 0 || M <= 0 || K < N) return SV_EARG;
+  if (K < 2) return SV_ESHAPE;
+  const int Bl = N * M;
+  hipLaunchKernelGGL(ge2e_calc_contrast_kernel, dim3((Bl + 3) / 4), dim3(256), 0, stream, S, Bl, M, K, per);
+  SV_LAUNCH_CHECK();
+  if (loss) {
+    hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(256), 0, stream, per, Bl, loss);
+    SV_LAUNCH_CHECK();
+  }
+  return SV_OK;
+}
+
+extern "C" int sv_ge2e_calc_contrast_bwd(const float* S, int N, int M, int K, const float* gloss, const float* gper,
+                                         float* dS, hipStream_t stream) {
+  if (!S || !dS || N <= 0 || M <= 0 || K < N) return SV_EARG;
+  if (K < 2) return SV_ESHAPE;
+  const int Bl = N * M;
+  hipLaunchKernelGGL(ge2e_calc_contrast_bwd_kernel, dim3((Bl + 3) / 4), dim3(256), 0, stream, S, Bl, M, K, gloss, gper,
+                     dS);
+  SV_LAUNCH_CHECK();
   return SV_OK;
 }
 

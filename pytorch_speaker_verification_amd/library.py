@@ -9,9 +9,10 @@ shapes instead of opaque Python.
         its backward (train_speech_embedder.py:62); it runs the forward again with the activations
         saved, then the BPTT kernels -- activation recomputation, as torch.utils.checkpoint does,
         because a custom op's outputs must be tensors and the saved state is ~6 GB of them at c2
-    sv::ge2e_loss(E, w, b) -> (loss, per)
-        GE2ELoss.forward (speech_embedder_net.py:43-49, utils.py:27-132)
-    sv::ge2e_loss_backward(E, w, b, gloss) -> (dE, dw, db)
+    sv::ge2e_loss(E, w, b, loss_method="softmax") -> (loss, per)
+        GE2ELoss.forward (speech_embedder_net.py:43-49, utils.py:27-132); loss_method "contrast":
+        the GE2E paper's contrast loss (eq. 7) on the same similarity matrix
+    sv::ge2e_loss_backward(E, w, b, gloss, loss_method="softmax") -> (dE, dw, db)
         its closed-form backward (SURVEY §8 a-G); recomputes the GE2E forward (~20 us)
 
 Autograd is registered on the forward ops (``register_autograd``), fake implementations on all
@@ -103,35 +104,38 @@ speech_embedder.register_autograd(_emb_backward, setup_context=_emb_setup)
 
 
 @torch.library.custom_op("sv::ge2e_loss", mutates_args=(), device_types="cuda")
-def ge2e_loss(E: Tensor, w: Tensor, b: Tensor) -> Tuple[Tensor, Tensor]:
-    loss, per, _ = ops.ge2e_forward(E.contiguous(), w, b)
+def ge2e_loss(E: Tensor, w: Tensor, b: Tensor, loss_method: str = "softmax") -> Tuple[Tensor, Tensor]:
+    loss, per, _ = ops.ge2e_forward(E.contiguous(), w, b, loss_method)
     return loss, per
 
 
 @ge2e_loss.register_fake
-def _(E, w, b):
+def _(E, w, b, loss_method="softmax"):
     return E.new_empty((), dtype=torch.float32), E.new_empty(E.shape[:2], dtype=torch.float32)
 
 
 @torch.library.custom_op("sv::ge2e_loss_backward", mutates_args=(), device_types="cuda")
-def ge2e_loss_backward(E: Tensor, w: Tensor, b: Tensor, gloss: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
-    _, _, st = ops.ge2e_forward(E.contiguous(), w, b)
+def ge2e_loss_backward(E: Tensor, w: Tensor, b: Tensor, gloss: Tensor,
+                       loss_method: str = "softmax") -> Tuple[Tensor, Tensor, Tensor]:
+    _, _, st = ops.ge2e_forward(E.contiguous(), w, b, loss_method)
     dE, dw, db = ops.ge2e_backward(st, w, b, gloss.reshape(()).to(torch.float32))
     return dE, dw.reshape(w.shape).clone(), db.reshape(b.shape).clone()
 
 
 @ge2e_loss_backward.register_fake
-def _(E, w, b, gloss):
+def _(E, w, b, gloss, loss_method="softmax"):
     return torch.empty_like(E, dtype=torch.float32), torch.empty_like(w), torch.empty_like(b)
 
 
 def _ge2e_setup(ctx, inputs, output):
-    ctx.save_for_backward(*inputs)
+    E, w, b, *rest = inputs  # (the schema's default fills loss_method in for three-argument calls)
+    ctx.save_for_backward(E, w, b)
+    ctx.loss_method = rest[0] if rest else "softmax"
 
 
 def _ge2e_backward(ctx, gloss, _gper):
     E, w, b = ctx.saved_tensors
-    return ge2e_loss_backward(E, w, b, gloss)
+    return (*ge2e_loss_backward(E, w, b, gloss, ctx.loss_method), None)
 
 
 ge2e_loss.register_autograd(_ge2e_backward, setup_context=_ge2e_setup)

@@ -19,7 +19,7 @@ import ctypes
 import torch
 
 from ._lib import (SV_DTYPE_BF16, SV_DTYPE_F32, SV_SCHED_CNT_READY, SV_SCHED_NO_EVENTS, SV_SCHED_WT_READY,
-                   PersistStatus, call, lib, ptr, require_device, schedule_flags, stream_of)
+                   PersistStatus, call, call_as, lib, loss_id, ptr, require_device, schedule_flags, stream_of)
 
 # timesteps per chunk of the layer-pipelined schedules (measured at c2: 16 / 24 / 32 / 48 / 64 ->
 # 69.3 / 69.7 / 69.1 / 69.5 / 69.6 ms per step)
@@ -615,11 +615,21 @@ def _pad_d(E):
     return Ep, D
 
 
-def ge2e_forward(E, w, b):
-    """GE2E loss of E [N,M,D] with device scalars w, b.  Returns (loss 0-dim, per [N,M], state)."""
+def _loss_kind(loss_method, N):
+    """The C ABI's loss id of a method name; the contrast loss needs a negative (N >= 2)."""
+    kind = loss_id(loss_method)
+    if loss_method == "contrast" and N < 2:
+        raise ValueError("the GE2E contrast loss needs N >= 2 speakers (max over k != j)")
+    return kind
+
+
+def ge2e_forward(E, w, b, loss_method="softmax"):
+    """GE2E loss of E [N,M,D] with device scalars w, b.  Returns (loss 0-dim, per [N,M], state).
+    loss_method: 'softmax' (eq. 6 of the GE2E paper, the reference's) or 'contrast' (eq. 7)."""
     require_device(E, w, b)
     if E.dim() != 3 or E.shape[1] < 2:
         raise ValueError("GE2E expects embeddings [N, M, D] with M >= 2 (leave-one-out centroids)")
+    kind = _loss_kind(loss_method, E.shape[0])
     Ep, D0 = _pad_d(E)
     N, M, D = Ep.shape
     dev = E.device
@@ -628,15 +638,22 @@ def ge2e_forward(E, w, b):
     st.ws = _ws(lib().sv_ge2e_workspace_size(N, M, D, N), dev)
     st.ssum = torch.empty((N, D), dtype=torch.float32, device=dev)
     st.N, st.M, st.D, st.D0 = N, M, D, D0
+    st.loss_method = loss_method
     loss = torch.empty((), dtype=torch.float32, device=dev)
     per = torch.empty((N, M), dtype=torch.float32, device=dev)
-    call("sv_ge2e_fwd", ptr(Ep), N, M, D, ptr(w.contiguous()), ptr(b.contiguous()), ptr(loss), ptr(per), ptr(st.ws),
-         ptr(st.ssum), s)
+    call_as("sv_ge2e_fwd", kind, ptr(Ep), N, M, D, ptr(w.contiguous()), ptr(b.contiguous()), ptr(loss), ptr(per),
+            ptr(st.ws), ptr(st.ssum), s)
     return loss, per, st
 
 
-def ge2e_backward(st, w, b, gloss=None):
-    """Returns (dE [N,M,D0], dw 0-dim, db 0-dim)."""
+def ge2e_backward(st, w, b, gloss=None, loss_method=None):
+    """Returns (dE [N,M,D0], dw 0-dim, db 0-dim).  loss_method: None = the forward's (the state
+    carries it); naming another one than the forward ran is an error."""
+    if loss_method is None:
+        loss_method = st.loss_method
+    elif loss_method != st.loss_method:
+        raise ValueError(f"ge2e_backward: the forward ran loss_method={st.loss_method!r}, not {loss_method!r}")
+    kind = loss_id(loss_method)
     N, M, D = st.N, st.M, st.D
     dev = st.ws.device
     s = stream_of(st.ws)
@@ -646,25 +663,27 @@ def ge2e_backward(st, w, b, gloss=None):
     dchat = torch.empty((Np, D), dtype=torch.float32, device=dev)
     beta = torch.empty((N,), dtype=torch.float32, device=dev)
     g = None if gloss is None else gloss.contiguous()
-    call("sv_ge2e_bwd", N, M, D, ptr(w.contiguous()), ptr(b.contiguous()), ptr(g), ptr(dE), ptr(dwdb), ptr(dchat),
-         ptr(beta), ptr(st.ws), s)
+    call_as("sv_ge2e_bwd", kind, N, M, D, ptr(w.contiguous()), ptr(b.contiguous()), ptr(g), ptr(dE), ptr(dwdb),
+            ptr(dchat), ptr(beta), ptr(st.ws), s)
     if st.D0 != D:
         dE = dE[..., :st.D0].contiguous()
     return dE, dwdb[0], dwdb[1]
 
 
-def ge2e_train(E, w, b, dwdb_out=None):
+def ge2e_train(E, w, b, dwdb_out=None, loss_method="softmax"):
     """Fused GE2E forward + closed-form backward for one GPU holding all N speakers (the training
     step's gloss = 1): returns (loss 0-dim, per [N,M], dE [N,M,D], dwdb [2]) from three launches
     (include/sv_ge2e.h, sv_ge2e_train); dwdb_out (2 contiguous fp32 on the device): written in
-    place of a new dwdb tensor.  Shapes outside sv_ge2e_train_ok take the split path."""
+    place of a new dwdb tensor.  Shapes outside sv_ge2e_train_ok take the split path.
+    loss_method: 'softmax' or 'contrast' (ge2e_forward)."""
     require_device(E, w, b)
     Ep, D0 = _pad_d(E)
     N, M, D = Ep.shape
     if M < 2:
         raise ValueError("GE2E expects embeddings [N, M, D] with M >= 2 (leave-one-out centroids)")
+    kind = _loss_kind(loss_method, N)
     if not lib().sv_ge2e_train_ok(N, M, D):
-        loss, per, st = ge2e_forward(E, w, b)
+        loss, per, st = ge2e_forward(E, w, b, loss_method)
         dE, dw, db = ge2e_backward(st, w, b)
         return loss, per, dE, torch.stack([dw, db])
     dev = E.device
@@ -675,8 +694,8 @@ def ge2e_train(E, w, b, dwdb_out=None):
     dwdb = torch.empty((2,), dtype=torch.float32, device=dev) if dwdb_out is None else dwdb_out
     if dwdb.numel() != 2 or dwdb.dtype != torch.float32 or not dwdb.is_contiguous() or dwdb.device != dev:
         raise ValueError("ge2e_train: dwdb_out must be 2 contiguous fp32 values on the embeddings' device")
-    call("sv_ge2e_train", ptr(Ep), N, M, D, ptr(w.contiguous()), ptr(b.contiguous()), ptr(loss), ptr(per), ptr(dE),
-         ptr(dwdb), ptr(ws), stream_of(Ep))
+    call_as("sv_ge2e_train", kind, ptr(Ep), N, M, D, ptr(w.contiguous()), ptr(b.contiguous()), ptr(loss), ptr(per),
+            ptr(dE), ptr(dwdb), ptr(ws), stream_of(Ep))
     if D0 != D:
         dE = dE[..., :D0].contiguous()
     return loss, per, dE, dwdb
@@ -684,8 +703,10 @@ def ge2e_train(E, w, b, dwdb_out=None):
 
 class GE2EFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, E, w, b):
-        loss, per, st = ge2e_forward(E, w, b)
+    def forward(ctx, E, w, b, *loss_method):
+        # apply(E, w, b) or apply(E, w, b, loss_method): the backward returns one gradient per input
+        loss, per, st = ge2e_forward(E, w, b, *loss_method)
+        ctx.n_extra = len(loss_method)
         ctx.st = st
         ctx.save_for_backward(w, b)
         ctx.mark_non_differentiable(per)
@@ -696,7 +717,7 @@ class GE2EFunction(torch.autograd.Function):
         w, b = ctx.saved_tensors
         dE, dw, db = ge2e_backward(ctx.st, w, b, gloss.reshape(()).to(torch.float32))
         ctx.st = None
-        return dE, dw.reshape(w.shape), db.reshape(b.shape)
+        return (dE, dw.reshape(w.shape), db.reshape(b.shape)) + (None,) * ctx.n_extra
 
 
 # ----------------------------------------------------------------------------- clip + SGD

@@ -21,11 +21,15 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
-from ._lib import call, lib, ptr, stream_of
+from ._lib import call, call_as, lib, loss_id, ptr, stream_of
 
 
 class HipShardKernels:
-    """Per-shard GE2E steps on the C ABI (sv_ge2e_speaker_sums / fwd_rows / bwd_rows / finalize)."""
+    """Per-shard GE2E steps on the C ABI (sv_ge2e_speaker_sums / fwd_rows / bwd_rows / finalize);
+    loss_method 'contrast' runs the row steps of the `_as` entry points."""
+
+    def __init__(self, loss_method="softmax"):
+        self.loss_method, self.kind = loss_method, loss_id(loss_method)
 
     def speaker_sums(self, E):
         Nl, M, D = E.shape
@@ -38,8 +42,8 @@ class HipShardKernels:
         ws = torch.empty(lib().sv_ge2e_workspace_size(Nl, M, D, N) // 4 + 1, dtype=torch.float32, device=E.device)
         per = torch.empty((Nl, M), dtype=torch.float32, device=E.device)
         loss = torch.empty((), dtype=torch.float32, device=E.device)
-        call("sv_ge2e_fwd_rows", ptr(E), Nl, M, D, s0, N, ptr(ssum_all), ptr(w), ptr(b), ptr(per), ptr(loss), ptr(ws),
-             stream_of(E))
+        call_as("sv_ge2e_fwd_rows", self.kind, ptr(E), Nl, M, D, s0, N, ptr(ssum_all), ptr(w), ptr(b), ptr(per),
+                ptr(loss), ptr(ws), stream_of(E))
         return loss, per, {"ws": ws, "shape": (Nl, M, D), "s0": s0, "N": N}
 
     def bwd_rows(self, st, w, b, gloss):
@@ -50,8 +54,8 @@ class HipShardKernels:
         # one buffer so the caller can all_reduce dC^ and beta together
         red = torch.empty(Np * D + N, dtype=torch.float32, device=dev)
         dwdb = torch.empty(2, dtype=torch.float32, device=dev)
-        call("sv_ge2e_bwd_rows", Nl, M, D, st["s0"], N, ptr(w), ptr(b), ptr(gloss), ptr(red), ptr(red[Np * D:]),
-             ptr(dwdb), ptr(st["ws"]), stream_of(red))
+        call_as("sv_ge2e_bwd_rows", self.kind, Nl, M, D, st["s0"], N, ptr(w), ptr(b), ptr(gloss), ptr(red),
+                ptr(red[Np * D:]), ptr(dwdb), ptr(st["ws"]), stream_of(red))
         return red, dwdb
 
     def finalize(self, st, red):
@@ -67,7 +71,11 @@ class HipShardKernels:
 class HipFusedShard:
     """The fused GE2E kernels in the speaker-sharded form (sv_ge2e_shard_prep / _rows /
     _finalize): 3 launches + the centroid pass around the two exchanges, for global N <= 256
-    (sv_ge2e_train_ok); the split kernels above for the rest."""
+    (sv_ge2e_train_ok); the split kernels above for the rest.  loss_method 'contrast' swaps the
+    rows step (sv_ge2e_shard_rows_as)."""
+
+    def __init__(self, loss_method="softmax"):
+        self.loss_method, self.kind = loss_method, loss_id(loss_method)
 
     @staticmethod
     def ok(N, M, D):
@@ -88,8 +96,8 @@ class HipFusedShard:
         red = torch.empty(Np * D + N, dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         dwdb = torch.empty(2, dtype=torch.float32, device=dev)
-        call("sv_ge2e_shard_rows", Nl, M, D, s0, N, ptr(ssum_all), ptr(w), ptr(b), ptr(per), ptr(red), ptr(loss),
-             ptr(dwdb), ptr(ws), stream_of(E))
+        call_as("sv_ge2e_shard_rows", self.kind, Nl, M, D, s0, N, ptr(ssum_all), ptr(w), ptr(b), ptr(per), ptr(red),
+                ptr(loss), ptr(dwdb), ptr(ws), stream_of(E))
         return loss, per, red, dwdb
 
     def finalize(self, E, s0, N, red, ws):
@@ -115,8 +123,12 @@ def all_gather_rows(x, rank, world, group=None):
 
 
 class ShardedGE2E:
-    def __init__(self, kernels=None, group=None):
-        self.k = kernels if kernels is not None else HipShardKernels()
+    def __init__(self, kernels=None, group=None, loss_method="softmax"):
+        """loss_method ('softmax' | 'contrast') selects the row step of the HIP kernels; a plugged-in
+        ``kernels`` object computes whatever loss it implements."""
+        loss_id(loss_method)  # ValueError for an unknown name
+        self.loss_method = loss_method
+        self.k = kernels if kernels is not None else HipShardKernels(loss_method)
         self.group = group
         if dist.is_available() and dist.is_initialized():
             self.rank = dist.get_rank(group)
@@ -149,13 +161,13 @@ class ShardedGE2E:
         exchange protocol above."""
         if self.world == 1 and isinstance(self.k, HipShardKernels):
             from .ops import ge2e_train
-            loss, _, dE, dwdb = ge2e_train(E_local, w, b, dwdb_out=dwdb_out)
+            loss, _, dE, dwdb = ge2e_train(E_local, w, b, dwdb_out=dwdb_out, loss_method=self.k.loss_method)
             return loss, dE, dwdb
         Nl, M, D = E_local.shape
         N = Nl * self.world
         if isinstance(self.k, HipShardKernels) and D % 4 == 0 and HipFusedShard.ok(N, M, D):
             # fused sharded form: prep -> all-gather sums -> rows -> all-reduce(dC^, beta) -> dE
-            f = HipFusedShard()
+            f = HipFusedShard(self.k.loss_method)
             E = E_local.contiguous()
             s0 = Nl * self.rank
             ssum_local, ws = f.prep(E, N)

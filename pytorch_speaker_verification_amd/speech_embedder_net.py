@@ -15,10 +15,10 @@ import math
 import torch
 import torch.nn as nn
 
-from ._lib import compute_device
+from ._lib import compute_device, loss_id
 from .hparam import hparam as hp
 from .ops import EmbedderFunction, GE2EFunction
-from .utils import calc_loss, get_centroids, get_cossim  # noqa: F401  (re-exports, as :13)
+from .utils import calc_loss, calc_loss_contrast, get_centroids, get_cossim  # noqa: F401  (re-exports, as :13)
 
 
 class LSTMStack(nn.Module):
@@ -98,13 +98,17 @@ class SpeechEmbedder(nn.Module):
 
 
 class GE2ELoss(nn.Module):
-    """GE2E softmax loss (speech_embedder_net.py:35-49) with learnable w=10, b=-5.
+    """GE2E loss (speech_embedder_net.py:35-49) with learnable w=10, b=-5: the softmax loss the
+    reference implements (``loss_method="softmax"``, the paper's eq. 6) or the paper's contrast loss
+    (``loss_method="contrast"``, eq. 7: 1 - sigma(S_jj) + max_{k != j} sigma(S_jk) per row).
 
     The reference's ``torch.clamp(self.w, 1e-6)`` discards its result (:44),
     so it is a no-op and is not reproduced.  The loss is the SUM over all N*M rows."""
 
-    def __init__(self, device):
+    def __init__(self, device, loss_method="softmax"):
         super().__init__()
+        loss_id(loss_method)  # ValueError for an unknown name
+        self.loss_method = loss_method
         self.w = nn.Parameter(torch.tensor(10.0).to(device), requires_grad=True)
         self.b = nn.Parameter(torch.tensor(-5.0).to(device), requires_grad=True)
         self.device = device
@@ -117,8 +121,10 @@ class GE2ELoss(nn.Module):
             fn = library.ge2e_loss
         else:
             fn = GE2EFunction.apply
+        # (the softmax call keeps its three-argument form)
+        extra = () if self.loss_method == "softmax" else (self.loss_method,)
         if self.w.is_cuda:
-            loss, _ = fn(embeddings.to(dev).contiguous(), self.w, self.b)
+            loss, _ = fn(embeddings.to(dev).contiguous(), self.w, self.b, *extra)
             return loss
-        loss, _ = fn(embeddings.to(dev).contiguous(), self.w.to(dev), self.b.to(dev))
+        loss, _ = fn(embeddings.to(dev).contiguous(), self.w.to(dev), self.b.to(dev), *extra)
         return loss.to(self.w.device)

@@ -15,6 +15,9 @@
     threshold sweep on device (exact integer counts, sv_eer_counts) and the reference's float32
     FAR/FRR/EER selection.  Returns the average EER (the reference only prints it).
 
+``train`` takes ``loss_method="softmax"``: ``"contrast"`` trains with the GE2E paper's contrast loss
+(eq. 7), which the reference does not implement, through the same step (GE2ELoss.loss_method).
+
 Both take ``dataset=None``: a given dataset replaces the configured one -- the way to train or
 evaluate the reference's raw-waveform configuration (``data_preprocessed: false``) on decoded audio,
 with ``data_load.SpeakerDatasetWaveforms``, whose batches are made on the GPU and skip the pinned copy.
@@ -56,14 +59,14 @@ def _loader(dataset, split, pin_memory):
                       drop_last=True, pin_memory=pin_memory and not on_device)
 
 
-def train(model_path, dataset=None):
+def train(model_path, dataset=None, loss_method="softmax"):
     device = torch.device(hp.device)
     train_dataset = _dataset() if dataset is None else dataset
     loader = _loader(train_dataset, hp.train, True)
     embedder_net = SpeechEmbedder().to(device)
     if hp.train.restore:
         embedder_net.load_state_dict(torch.load(model_path, weights_only=True))
-    ge2e_loss = GE2ELoss(device)
+    ge2e_loss = GE2ELoss(device, loss_method=loss_method)
     trainer = GE2ETrainer(embedder_net, ge2e_loss, lr=hp.train.lr)
     os.makedirs(hp.train.checkpoint_dir, exist_ok=True)
     N, M = hp.train.N, hp.train.M

@@ -83,7 +83,8 @@ class GE2ETrainer:
         self.lr, self.clip_net, self.clip_wb = float(lr), float(clip_net), float(clip_wb)
         self.group = group
         self.write_grads = write_grads
-        self.ge2e = ShardedGE2E(group=group)
+        # the loss module names the GE2E loss ('softmax' | 'contrast'; GE2ELoss.loss_method)
+        self.ge2e = ShardedGE2E(group=group, loss_method=getattr(ge2e_loss, "loss_method", "softmax"))
         # the data-parallel machinery (comm stream, bucketed SUM all-reduce from the backward's
         # events, status flags): on whenever the group has more than one rank; a world-1 process
         # group may switch it on to run the collectives on one GPU (tests/test_gpu_rccl.py)

@@ -1,7 +1,7 @@
 """Drop-in GE2E helpers (reference utils.py:27-132) on the HIP kernels.
 
 ``get_centroids``, ``get_cossim`` and ``calc_loss`` keep the reference's names, argument
-meaning and output shapes, and they are differentiable like the reference's autograd ops: a loss
+meaning and output shapes (``calc_loss_contrast`` is the paper's contrast loss beside them), and they are differentiable like the reference's autograd ops: a loss
 composed from them as ``GE2ELoss.forward`` does (speech_embedder_net.py:45-48) trains, with the
 backward in HIP kernels (include/sv_ge2e.h, sv_ge2e_*_bwd).  They are also the stand-alone forms
 used outside the training loss (the EER evaluation, train_speech_embedder.py:127-129).  Inputs
@@ -109,6 +109,34 @@ class _CalcLoss(torch.autograd.Function):
         return dS.to(ctx.home)
 
 
+class _CalcLossContrast(torch.autograd.Function):
+    """(loss, per) = calc_loss_contrast(S): per = 1 - sigma(S[j,i,j]) + max_{k != j} sigma(S[j,i,k])
+    (GE2E paper eq. 7); backward dS[j] = -g p (1 - p), dS[k*] = g q (1 - q), 0 elsewhere, g = gloss +
+    gper_ji (sv_ge2e_calc_contrast / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, S):
+        home, dev = S.device, compute_device(S)
+        Sd = _dev(S, dev)
+        N, M, K = Sd.shape
+        per = torch.empty((N, M), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        call("sv_ge2e_calc_contrast", ptr(Sd), N, M, K, ptr(per), ptr(loss), stream_of(Sd))
+        ctx.save_for_backward(Sd)
+        ctx.home, ctx.dev = home, dev
+        return loss.to(home), per.to(home)
+
+    @staticmethod
+    def backward(ctx, gloss, gper):
+        (Sd,) = ctx.saved_tensors
+        N, M, K = Sd.shape
+        gl = None if gloss is None else _dev(gloss.reshape(1), ctx.dev)
+        gp = None if gper is None else _dev(gper, ctx.dev)
+        dS = torch.empty_like(Sd)
+        call("sv_ge2e_calc_contrast_bwd", ptr(Sd), N, M, K, ptr(gl), ptr(gp), ptr(dS), stream_of(Sd))
+        return dS.to(ctx.home)
+
+
 def get_centroids(embeddings):
     """C[j] = mean_i E[j, i]  (utils.py:27-29).  [N,M,D] -> [N,D]."""
     return _Centroids.apply(embeddings)
@@ -129,3 +157,12 @@ def calc_loss(sim_matrix):
     """(loss, per_embedding_loss[N,M]) with per = log(sum_k e^S + 1e-6) - S[j,i,j]
     (utils.py:126-132)."""
     return _CalcLoss.apply(sim_matrix)
+
+
+def calc_loss_contrast(sim_matrix):
+    """(loss, per_embedding_loss[N,M]) of the GE2E contrast loss (arXiv 1710.10467 eq. 7; the
+    reference implements only the softmax): per = 1 - sigma(S[j,i,j]) + max_{k != j} sigma(S[j,i,k]),
+    the maximum where S is largest, ties to the lowest k.  S [N,M,K] with K >= N and K >= 2."""
+    if sim_matrix.dim() != 3 or sim_matrix.shape[2] < max(2, sim_matrix.shape[0]):
+        raise ValueError("calc_loss_contrast expects S [N, M, K] with K >= N and K >= 2 (a negative per row)")
+    return _CalcLossContrast.apply(sim_matrix)
