@@ -12,57 +12,15 @@
 //   cos[r, s(r)] := <E^_r, U^_r>, U_r = (Ssum_s(r) - E_r) / (M - 1)   (leave-one-out)
 //   S = w (cos + 1e-6) + b;  per_r = log(sum_k e^S + 1e-6) - S[r, s(r)];  loss = sum per
 // with x^ = x / max(|x|, 1e-8) (torch cosine_similarity).
-#include <algorithm>
-#include "sv_common.h"
-#include "../../include/sv_ge2e.h"
-
-#define EPS_COS 1e-8f
-#define EPS_SIM 1e-6f
-#define EPS_LOG 1e-6f
-
-namespace {
-
-// workspace carve (all fp32), see sv_ge2e_workspace_size
-struct Ge2eWs {
-  float *Ehat, *Uhat, *En, *Un, *rawd, *cos, *logz, *Chat, *Cn, *dcos, *alpha, *G1, *dwdb_rows, *betap, *dcd, *gemm;
-  size_t total;
-};
-
-size_t al(size_t n) { return (n + 63) & ~size_t(63); }  // 256-byte granules
-
-Ge2eWs carve(float* base, int Nl, int M, int D, int N) {
-  Ge2eWs w;
-  N = (N + 3) & ~3;  // speaker dimension padded to a multiple of 4 (zero rows/cols)
-  const size_t Bl = (size_t)Nl * M;
-  size_t off = 0;
-  auto take = [&](size_t n) {
-    float* p = base ? base + off : nullptr;
-    off += al(n);
-    return p;
-  };
-  w.Ehat = take(Bl * D);
-  w.Uhat = take(Bl * D);
-  w.En = take(Bl);
-  w.Un = take(Bl);
-  w.rawd = take(Bl);
-  w.cos = take(Bl * N);
-  w.logz = take(Bl);
-  w.Chat = take((size_t)N * D);
-  w.Cn = take(N);
-  w.dcos = take(Bl * N);
-  w.alpha = take(Bl);
-  w.G1 = take(Bl * D);
-  w.dwdb_rows = take(2 * Bl);
-  w.betap = take(((Bl + 63) / 64) * (size_t)N);
-  w.dcd = take(Bl);
-  const size_t g1 = sv_gemm_f32_workspace((int)Bl, D, N);
-  const size_t g2 = sv_gemm_f32_workspace(N, D, (int)Bl);
-  w.gemm = take((std::max(g1, g2) + 3) / 4);
-  w.total = off * sizeof(float);
-  return w;
-}
-
-}  // namespace
+//
+// This file is the training path: the split kernels (K6 / K7: any shape, the cosines and Jacobians
+// by the fp32 MFMA GEMM), the fused kernels (F1 - F3 below, local and speaker-sharded) and the C ABI
+// over both, for the softmax and the contrast loss (`_as` entry points).  sv_ge2e_dev.h holds what
+// the kernels share (constants, the workspace, the row frame, the dE epilogue, the loss tail),
+// sv_ge2e_contrast.h the contrast loss's row arithmetic and its fused row kernel, and
+// sv_ge2e_utils.hip the stand-alone utils.py helpers and the EER counts.
+#include "sv_ge2e_dev.h"
+#include "sv_ge2e_contrast.h"
 
 // ---------------------------------------------------------------------------
 // K6a: per-speaker sums Ssum[j, :] = sum_i E[j, i, :]  (fixed order i = 0..M-1)
@@ -278,12 +236,7 @@ __global__ __launch_bounds__(256) void ge2e_dwdb_kernel(const float* __restrict_
   }
 }
 
-// K7d: finalize dE for one local speaker per block:
-//   dC_j  = (dChat_j - beta_j C^_j [|C|>eps]) / max(|C_j|, eps)
-//   dU_r  = dcos_d (E^_r - raw_d U^_r [|U|>eps]) / max(|U_r|, eps)
-//   dE_r  = (G1_r + dcos_d U^_r - alpha_r E^_r [|E|>eps]) / max(|E_r|, eps)
-//           + dC_j / M + (sum_i' dU_ji' - dU_r) / (M - 1)
-// where dcos_d = w dS[r, s(r)] is recovered from alpha_r's definition inputs.
+// K7d: finalize dE for one local speaker per block (the terms: sv_ge2e_dev.h, ge2e_dU .. ge2e_dE).
 // any M (the split path's general form): one thread per d walks the speaker's M rows twice
 __global__ __launch_bounds__(256) void ge2e_finalize_serial_kernel(
     int M, int D, int s0, const float* __restrict__ dchat, const float* __restrict__ beta,
@@ -293,36 +246,26 @@ __global__ __launch_bounds__(256) void ge2e_finalize_serial_kernel(
     const float* __restrict__ G1, float* __restrict__ dE) {
   const int j = blockIdx.x;
   const int sg = s0 + j;
-  const float cn = Cn[sg];
-  const float icn = 1.0f / fmaxf(cn, EPS_COS);
-  const float pc = cn > EPS_COS ? 1.f : 0.f;
+  const Ge2eNorm cn = ge2e_norm(Cn[sg]);
   const float bj = beta[sg];
-  const float invM = 1.0f / (float)M, invm1 = 1.0f / (float)(M - 1);
   for (int d = threadIdx.x; d < D; d += 256) {
     const long cd = (long)sg * D + d;
-    const float dC = (dchat[cd] - bj * Chat[cd] * pc) * icn;
+    const float dC = ge2e_dC(cn, dchat[cd], bj, Chat[cd]);
     float sumdU = 0.f;
     for (int i = 0; i < M; ++i) {
       const int r = j * M + i;
-      const float iu = 1.0f / fmaxf(Un[r], EPS_COS);
-      const float pu = Un[r] > EPS_COS ? 1.f : 0.f;
-      sumdU += dcd[r] * (Ehat[(long)r * D + d] - rawd[r] * Uhat[(long)r * D + d] * pu) * iu;
+      sumdU += ge2e_dU(ge2e_norm(Un[r]), dcd[r], Ehat[(long)r * D + d], rawd[r], Uhat[(long)r * D + d]);
     }
     for (int i = 0; i < M; ++i) {
       const int r = j * M + i;
       const long rd = (long)r * D + d;
-      const float iu = 1.0f / fmaxf(Un[r], EPS_COS);
-      const float pu = Un[r] > EPS_COS ? 1.f : 0.f;
-      const float dU = dcd[r] * (Ehat[rd] - rawd[r] * Uhat[rd] * pu) * iu;
-      const float ie = 1.0f / fmaxf(En[r], EPS_COS);
-      const float pe = En[r] > EPS_COS ? 1.f : 0.f;
-      const float gE = (G1[rd] + dcd[r] * Uhat[rd] - alpha[r] * Ehat[rd] * pe) * ie;
-      dE[rd] = gE + dC * invM + (sumdU - dU) * invm1;
+      const float dU = ge2e_dU(ge2e_norm(Un[r]), dcd[r], Ehat[rd], rawd[r], Uhat[rd]);
+      const float gE = ge2e_gE(ge2e_norm(En[r]), G1[rd], dcd[r], Uhat[rd], alpha[r], Ehat[rd]);
+      dE[rd] = ge2e_dE(gE, dC, sumdU, dU, M);
     }
   }
 }
 
-#define GF_MMAX_FIN 16  // utterances per speaker of the one-pass finalize (one wave each)
 __global__ __launch_bounds__(1024) void ge2e_finalize_kernel(
     int M, int D, int s0, const float* __restrict__ dchat, const float* __restrict__ beta,
     const float* __restrict__ Chat, const float* __restrict__ Cn, const float* __restrict__ Ehat,
@@ -343,38 +286,30 @@ __global__ __launch_bounds__(1024) void ge2e_finalize_kernel(
   float dU = 0.f, gE = 0.f;
   if (mine) {
     const float un = Un[r], en = En[r], dd = dcd[r];
-    const float iu = 1.0f / fmaxf(un, EPS_COS);
-    const float pu = un > EPS_COS ? 1.f : 0.f;
     const float eh = Ehat[rd], uh = Uhat[rd];
-    dU = dd * (eh - rawd[r] * uh * pu) * iu;
-    const float ie = 1.0f / fmaxf(en, EPS_COS);
-    const float pe = en > EPS_COS ? 1.f : 0.f;
-    gE = (G1[rd] + dd * uh - alpha[r] * eh * pe) * ie;
+    dU = ge2e_dU(ge2e_norm(un), dd, eh, rawd[r], uh);
+    gE = ge2e_gE(ge2e_norm(en), G1[rd], dd, uh, alpha[r], eh);
     dUs[i][lane] = dU;
   }
   __syncthreads();
   if (!mine) return;
-  const float cn = Cn[sg];
-  const float icn = 1.0f / fmaxf(cn, EPS_COS);
-  const float pc = cn > EPS_COS ? 1.f : 0.f;
   const long cd = (long)sg * D + d;
-  const float dC = (dchat[cd] - beta[sg] * Chat[cd] * pc) * icn;
+  const float dC = ge2e_dC(ge2e_norm(Cn[sg]), dchat[cd], beta[sg], Chat[cd]);
   float sumdU = 0.f;
   for (int k = 0; k < M; ++k) sumdU += dUs[k][lane];
-  const float invM = 1.0f / (float)M, invm1 = 1.0f / (float)(M - 1);
-  dE[rd] = gE + dC * invM + (sumdU - dU) * invm1;
+  dE[rd] = ge2e_dE(gE, dC, sumdU, dU, M);
 }
 
 // dE of a shard's speakers from the reduced [dC^ | beta]: the one-pass 2-D form up to GF_MMAX_FIN
 // utterances per speaker, else the serial form
 static void launch_finalize(int N_local, int M, int D, int s0, const float* dchat, const float* beta, const Ge2eWs& ws,
-                            const float* dcd, float* dE, hipStream_t stream) {
+                            float* dE, hipStream_t stream) {
   if (M <= GF_MMAX_FIN)
     hipLaunchKernelGGL(ge2e_finalize_kernel, dim3(N_local, (D + 63) / 64), dim3(64 * M), 0, stream, M, D, s0, dchat, beta,
-                       ws.Chat, ws.Cn, ws.Ehat, ws.Uhat, ws.En, ws.Un, ws.rawd, dcd, ws.alpha, ws.G1, dE);
+                       ws.Chat, ws.Cn, ws.Ehat, ws.Uhat, ws.En, ws.Un, ws.rawd, ws.dcd, ws.alpha, ws.G1, dE);
   else
     hipLaunchKernelGGL(ge2e_finalize_serial_kernel, dim3(N_local), dim3(256), 0, stream, M, D, s0, dchat, beta, ws.Chat,
-                       ws.Cn, ws.Ehat, ws.Uhat, ws.En, ws.Un, ws.rawd, dcd, ws.alpha, ws.G1, dE);
+                       ws.Cn, ws.Ehat, ws.Uhat, ws.En, ws.Un, ws.rawd, ws.dcd, ws.alpha, ws.G1, dE);
 }
 
 // dcos on the diagonal (w dS[r, s(r)]) for the finalize step, recomputed from logz
@@ -388,11 +323,79 @@ __global__ void ge2e_dcd_kernel(const float* __restrict__ rawd, const float* __r
   dcd[r] = w * g * (p - 1.0f);
 }
 
-#include "sv_ge2e_contrast.h"
+// ---- the contrast counterparts of ge2e_rowloss_kernel / ge2e_rowbwd_kernel / ge2e_dcd_kernel on
+// the GEMM-formed cos [Bl, ldc] (the row arithmetic: sv_ge2e_contrast.h).  One wave per row.  The
+// forward leaves k* (as integer bits) in the workspace slot that holds logz for the softmax; the
+// backward reads it back, so both pick the same column by construction.
+__global__ __launch_bounds__(256) void ge2e_rowloss_contrast_kernel(float* __restrict__ cos, const float* __restrict__ rawd,
+                                                                    int Bl, int M, int N, int ldc, int s0,
+                                                                    const float* __restrict__ wp,
+                                                                    const float* __restrict__ bp, float* __restrict__ per,
+                                                                    float* __restrict__ kst) {
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (r >= Bl) return;
+  const int sg = s0 + r / M;
+  const float w = *wp, b = *bp;
+  float* c = cos + (long)r * ldc;
+  const float rd = rawd[r];
+  if (lane == 0) c[sg] = rd;  // get_cossim's diagonal overwrite (no lane reads c[sg] below)
+  float bs = -INFINITY;
+  int bk = INT_MAX;
+  for (int k = lane; k < N; k += 64) {
+    const float s = w * (c[k] + EPS_SIM) + b;
+    if (k != sg && s > bs) {
+      bs = s;
+      bk = k;
+    }
+  }
+  ct_wave_argmax(bs, bk);
+  bk = ct_legal(bk, N, sg);
+  if (lane == 0) {
+    per[r] = ct_row(w, b, 1.0f, rd, c[bk]).per;
+    kst[r] = __int_as_float(bk);
+  }
+}
 
-static bool loss_known(int loss) { return loss == SV_GE2E_SOFTMAX || loss == SV_GE2E_CONTRAST; }
-// the contrast loss needs a negative: at least two speakers in the (global) batch
-static bool loss_shape_ok(int loss, int N) { return loss != SV_GE2E_CONTRAST || N >= 2; }
+__global__ __launch_bounds__(256) void ge2e_rowbwd_contrast_kernel(const float* __restrict__ cos, const float* __restrict__ kst,
+                                                                   int Bl, int M, int N, int ldc, int s0,
+                                                                   const float* __restrict__ wp,
+                                                                   const float* __restrict__ bp, const float* __restrict__ gl,
+                                                                   float* __restrict__ dcos, float* __restrict__ alpha,
+                                                                   float* __restrict__ dwdb) {
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (r >= Bl) return;
+  const int sg = s0 + r / M;
+  const float g = gl ? *gl : 1.0f;
+  const float* c = cos + (long)r * ldc;
+  const int bk = ct_legal(__float_as_int(kst[r]), N, sg);
+  const CtRow o = ct_row(*wp, *bp, g, c[sg], c[bk]);
+  float* dc = dcos + (long)r * ldc;
+  for (int k = lane; k < ldc; k += 64) dc[k] = (k == bk) ? o.dck : 0.f;
+  if (lane == 0) {
+    alpha[r] = o.alpha;
+    dwdb[r] = o.dw;
+    dwdb[Bl + r] = o.db;
+  }
+}
+
+// dcos on the diagonal, w g dS[r, s(r)] = -w g p (1 - p), for the finalize step
+__global__ void ge2e_dcd_contrast_kernel(const float* __restrict__ rawd, int Bl, const float* __restrict__ wp,
+                                         const float* __restrict__ bp, const float* __restrict__ gl,
+                                         float* __restrict__ dcd) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= Bl) return;
+  const float w = *wp, g = gl ? *gl : 1.0f;
+  dcd[r] = -w * g * ct_dsigmoid(w * (rawd[r] + EPS_SIM) + *bp);
+}
+
+// the `_as` entry points' first check: SV_EARG for an unknown loss id, then SV_ESHAPE where the
+// contrast loss has no negative (fewer than two speakers in the global batch)
+static int loss_args_check(int loss, int N) {
+  if (loss != SV_GE2E_SOFTMAX && loss != SV_GE2E_CONTRAST) return SV_EARG;
+  return loss == SV_GE2E_CONTRAST && N < 2 ? SV_ESHAPE : SV_OK;
+}
 
 // ============================================================================
 // C ABI
@@ -415,8 +418,7 @@ extern "C" int sv_ge2e_speaker_sums(const float* E, int N_local, int M, int D, f
 extern "C" int sv_ge2e_fwd_rows_as(int loss, const float* E, int N_local, int M, int D, int spk_offset, int N,
                                    const float* ssum_all, const float* w, const float* b, float* per, float* loss_local,
                                    float* workspace, hipStream_t stream) {
-  if (!loss_known(loss)) return SV_EARG;
-  if (!loss_shape_ok(loss, N)) return SV_ESHAPE;
+  if (int rc = loss_args_check(loss, N)) return rc;
   if (!ge2e_args_ok(E, N_local, M, D, spk_offset, N) || !ssum_all || !w || !b || !per || !workspace) return SV_EARG;
   const Ge2eWs ws = carve(workspace, N_local, M, D, N);
   const int Bl = N_local * M, Np = (N + 3) & ~3;
@@ -451,10 +453,10 @@ extern "C" int sv_ge2e_fwd_rows(const float* E, int N_local, int M, int D, int s
 
 extern "C" int sv_ge2e_fwd_as(int loss_kind, const float* E, int N, int M, int D, const float* w, const float* b,
                               float* loss, float* per, float* workspace, float* ssum, hipStream_t stream) {
-  if (!loss_known(loss_kind)) return SV_EARG;
-  if (!loss_shape_ok(loss_kind, N)) return SV_ESHAPE;
+  int rc = loss_args_check(loss_kind, N);
+  if (rc) return rc;
   if (!ssum) return SV_EARG;
-  int rc = sv_ge2e_speaker_sums(E, N, M, D, ssum, stream);
+  rc = sv_ge2e_speaker_sums(E, N, M, D, ssum, stream);
   if (rc) return rc;
   return sv_ge2e_fwd_rows_as(loss_kind, E, N, M, D, 0, N, ssum, w, b, per, loss, workspace, stream);
 }
@@ -467,8 +469,7 @@ extern "C" int sv_ge2e_fwd(const float* E, int N, int M, int D, const float* w, 
 extern "C" int sv_ge2e_bwd_rows_as(int loss, int N_local, int M, int D, int spk_offset, int N, const float* w,
                                    const float* b, const float* gloss, float* dchat_partial, float* beta_partial,
                                    float* dwdb, float* workspace, hipStream_t stream) {
-  if (!loss_known(loss)) return SV_EARG;
-  if (!loss_shape_ok(loss, N)) return SV_ESHAPE;
+  if (int rc = loss_args_check(loss, N)) return rc;
   if (N_local <= 0 || M < 2 || D <= 0 || N < N_local || !w || !b || !dchat_partial || !beta_partial || !dwdb ||
       !workspace)
     return SV_EARG;
@@ -496,13 +497,13 @@ extern "C" int sv_ge2e_bwd_rows_as(int loss, int N_local, int M, int D, int spk_
   SV_LAUNCH_CHECK();
   hipLaunchKernelGGL(ge2e_dwdb_kernel, dim3(1), dim3(256), 0, stream, ws.dwdb_rows, Bl, dwdb);
   SV_LAUNCH_CHECK();
-  // diagonal dcos into the (now free) dwdb_rows slot for the finalize step
+  // diagonal dcos for the finalize step
   if (loss == SV_GE2E_CONTRAST)
     hipLaunchKernelGGL(ge2e_dcd_contrast_kernel, dim3((Bl + 255) / 256), dim3(256), 0, stream, ws.rawd, Bl, w, b, gloss,
-                       ws.dwdb_rows);
+                       ws.dcd);
   else
     hipLaunchKernelGGL(ge2e_dcd_kernel, dim3((Bl + 255) / 256), dim3(256), 0, stream, ws.rawd, ws.logz, Bl, w, b, gloss,
-                       ws.dwdb_rows);
+                       ws.dcd);
   SV_LAUNCH_CHECK();
   return SV_OK;
 }
@@ -518,7 +519,7 @@ extern "C" int sv_ge2e_bwd_finalize(int N_local, int M, int D, int spk_offset, i
                                     const float* beta, float* dE, float* workspace, hipStream_t stream) {
   if (N_local <= 0 || M < 2 || D <= 0 || !dchat || !beta || !dE || !workspace) return SV_EARG;
   const Ge2eWs ws = carve(workspace, N_local, M, D, N);
-  launch_finalize(N_local, M, D, spk_offset, dchat, beta, ws, ws.dwdb_rows, dE, stream);
+  launch_finalize(N_local, M, D, spk_offset, dchat, beta, ws, dE, stream);
   SV_LAUNCH_CHECK();
   return SV_OK;
 }
@@ -544,19 +545,22 @@ extern "C" int sv_ge2e_bwd(int N, int M, int D, const float* w, const float* b, 
 //                         the diagonal cosine (a wave per row, shuffle reductions)
 //   F2 ge2e_rows_kernel   one wave per row, C^ of every speaker staged in LDS once per
 //                         workgroup: the row's N cosines (lanes over speakers, ds_read_b128 of
-//                         conflict-free padded C^ rows, E^ broadcast), the diagonal overwrite, the
-//                         shuffle softmax (max, log-sum-exp, per-row loss), dS = p - delta,
-//                         dcos, alpha, dw/db row partials and G1 = sum_k dcos_k C^_k
+//                         conflict-free padded C^ rows, E^ broadcast: the row frame of
+//                         sv_ge2e_dev.h), the diagonal overwrite, the shuffle softmax (max,
+//                         log-sum-exp, per-row loss), dS = p - delta, dcos, alpha, dcd, dw/db row
+//                         partials and G1 = sum_k dcos_k C^_k.  ge2e_rows4r_kernel at
+//                         128 < N <= 256, D = 256 (register-blocked, a frame of its own);
+//                         ge2e_rows_contrast_kernel (sv_ge2e_contrast.h) for the contrast loss: the
+//                         same frame, then an arg max in place of the softmax
 //   F3 ge2e_cols_kernel   one workgroup per (speaker k, 64-wide d slice): beta_k and
 //                         dC^_k = sum_r dcos[r,k] E^_r over every row, then dC_k and the speaker's
-//                         rows of dE (the split path's finalize); workgroup (0, 0) also sums the
-//                         loss and dw, db in fixed order
+//                         rows of dE (ge2e_dU .. ge2e_dE, as the finalize kernels); workgroup
+//                         (0, 0) also sums the loss and dw, db (ge2e_loss_tail)
 // The arithmetic is the split path's (same formulas, fixed-order sums; the cosines by FMA dot
-// products instead of the MFMA GEMM), so results agree to fp32 rounding.
+// products instead of the MFMA GEMM), so results agree to fp32 rounding.  The sharded form runs F1,
+// F2, then ge2e_cols_partial_kernel into the reduce buffer and, after the all-reduce,
+// ge2e_finalize_kernel.
 // ============================================================================
-#define GF_NMAX 256
-#define GF_DMAX 256
-#define GF_MMAX 16
 
 // ssum (sharded form): the speaker's sum goes out for the all-gather instead of C^ / |C| (the
 // centroids of every rank's speakers are formed after it by ge2e_centroid_kernel)
@@ -642,14 +646,12 @@ __global__ __launch_bounds__(256) void ge2e_prep_kernel(const float* __restrict_
 
 // F2: GF_ROWW rows per workgroup, one per wave (160 workgroups of 4 waves at c2: each row's
 // serial work in its own wave; 8 waves per workgroup measured slower, 11.2 vs 10.0 us at c2).
-// Cs [NT][D + 4] fp32 in LDS (16-B padded rows: the 16 lanes of a ds_read_b128 group hit
-// disjoint banks); the rows' E^ in Es [GF_ROWW][D]; per-row dcos in Vs [GF_ROWW][N].
+// The frame (Cs, Es, the tile stage and the cosine step) is sv_ge2e_dev.h's; per-row dcos in
+// Vs [GF_ROWW][N].
 // NH = 64-speaker groups per lane: 2 for N <= 128 (C^ staged once, NT = N), 4 for N <= 256 (c5's
 // "centroid LDS stress": 256 fp32 rows of C^ are 266 KB, over the 160 KB LDS), where C^ is staged
 // in two tiles of GF_TILE = 128 speakers (133 KB): tile 0, then tile 1 for the cosines, G1 over
 // tile 1 while it is resident, then tile 0 again -- still fp32 throughout.
-#define GF_ROWW 4
-#define GF_TILE 128
 template <int NH>
 __global__ __launch_bounds__(64 * GF_ROWW) void ge2e_rows_kernel(const float* __restrict__ Chat, const float* __restrict__ Ehat,
                                                         const float* __restrict__ rawd, int Bl, int M, int N, int D,
@@ -666,29 +668,7 @@ __global__ __launch_bounds__(64 * GF_ROWW) void ge2e_rows_kernel(const float* __
   float* Es = Cs + (size_t)NT * LDC;     // [GF_ROWW][D]
   float* Vs = Es + GF_ROWW * D;          // [GF_ROWW][N]
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int D4 = D / 4;
-  // global -> LDS copy of C^ rows k0 .. .  D = 256 (every c1-c5 shape): by LDS-DMA, one 1 KB row per
-  // wave instruction (no VGPR round trip, every row in flight at once; the register copy below kept
-  // ~8 loads per lane in flight and took ~12 us per 128-speaker tile at c5's rank shape), waited for
-  // by the caller's vmcnt(0) + barrier; else through registers (distinct address spaces: the unrolled
-  // loads issue back to back)
-  auto stage = [&](int k0) {
-    const int nk = min(NT, N - k0);
-    if (D == 256) {
-      for (int row = w; row < nk; row += GF_ROWW)
-        __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)(Chat + (long)(k0 + row) * D + lane * 4),
-                                         (__attribute__((address_space(3))) void*)(Cs + row * LDC), 16, 0, 0);
-      return;
-    }
-    const int NQ = nk * D4;
-#pragma unroll 8
-    for (int q = tid; q < NQ; q += 64 * GF_ROWW) {
-      const int row = q / D4, col = (q - row * D4) * 4;
-      *reinterpret_cast<float4*>(Cs + row * LDC + col) =
-          *reinterpret_cast<const float4*>(Chat + (long)(k0 + row) * D + col);
-    }
-  };
-  stage(0);
+  ge2e_stage_tile<GF_ROWW>(Chat, Cs, 0, NT, N, D);
   const int r = blockIdx.x * GF_ROWW + w;   // this wave's row
   const bool live = r < Bl;
   if (live)
@@ -702,44 +682,8 @@ __global__ __launch_bounds__(64 * GF_ROWW) void ge2e_rows_kernel(const float* __
   const float wv = *wp, bv = *bp;
   const int sg = s0 + r / M;  // global speaker of this row (s0: the shard's first)
   const float rd = live ? rawd[r] : 0.f;
-  // cosines: KS speaker lanes x DS d-slices (DS = 1 for N > 32: lane k and k + 64 over all of
-  // D; small N splits D so the wave's lanes all work, the slices then meet by a butterfly), E^
-  // broadcast; four independent partial sums (d mod 4), added pairwise at the end.  Speaker
-  // lane + 64 h is cv[h].
-  int DS = N <= 8 ? 8 : N <= 16 ? 4 : N <= 32 ? 2 : 1;
-  while (DS > 1 && D % (4 * DS)) DS >>= 1;
-  const int KS = 64 / DS, dlen = D / DS;
-  const int kl = lane & (KS - 1), d0 = (lane / KS) * dlen;
   float cv[NH];
-#pragma unroll
-  for (int h = 0; h < NH; ++h) cv[h] = 0.f;
-  const float* e0 = Es + w * D;
-#pragma unroll
-  for (int t = 0; t < NH / 2; ++t) {
-    if (t > 0) {  // NH == 4: the second tile
-      __syncthreads();
-      stage(t * GF_TILE);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-    }
-#pragma unroll
-    for (int hk = 0; hk < 2; ++hk) {
-      const int kt = kl + 64 * hk;  // speaker within the tile
-      if (live && t * GF_TILE + kt < N) {
-        float4 a = float4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 8
-        for (int c = d0; c < d0 + dlen; c += 4) {
-          const float4 cc = *reinterpret_cast<const float4*>(Cs + kt * LDC + c);
-          const float4 x0 = *reinterpret_cast<const float4*>(e0 + c);
-          a.x += x0.x * cc.x;
-          a.y += x0.y * cc.y;
-          a.z += x0.z * cc.z;
-          a.w += x0.w * cc.w;
-        }
-        cv[2 * t + hk] = (a.x + a.y) + (a.z + a.w);
-      }
-    }
-  }
+  const int KS = ge2e_cos_step<NH, GF_ROWW>(Chat, Cs, Es + w * D, live, NT, N, D, cv);
   for (int o = KS; o < 64; o <<= 1) cv[0] += __shfl_xor(cv[0], o, 64);  // lane k < KS: speaker k
 #pragma unroll
   for (int h = 0; h < NH; ++h)
@@ -819,19 +763,13 @@ __global__ __launch_bounds__(64 * GF_ROWW) void ge2e_rows_kernel(const float* __
   } else {
     if (cok) g1_acc(GF_TILE, N, GF_TILE);  // tile 1 is resident
     __syncthreads();
-    stage(0);
+    ge2e_stage_tile<GF_ROWW>(Chat, Cs, 0, NT, N, D);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (cok) g1_acc(0, GF_TILE, 0);
   }
   if (cok) *reinterpret_cast<float4*>(G1 + (long)r * D + c) = float4{g0.x + g1.x, g0.y + g1.y, g0.z + g1.z, g0.w + g1.w};
 }
-
-constexpr int GF_CH = 128;  // speakers per chunk of ge2e_rows4r_kernel
-
-// ge2e_rows4r_kernel's centroid tile stride: 288 = 32 mod 64 banks, so the two speakers of a 16-lane
-// LDS pass (8-lane groups reading 32 consecutive floats each) fall on disjoint banks
-constexpr int GF_R4LDC = 288;
 
 // a workgroup-uniform value (read from LDS) kept in an SGPR
 __device__ __forceinline__ float uniform_f(float v) {
@@ -1098,11 +1036,11 @@ __global__ __launch_bounds__(64 * NWV) void ge2e_rows4r_kernel(const float* __re
   }
 }
 
-// rows per workgroup of ge2e_rows_contrast_kernel above CT_TILE speakers: the fewest of 4 / 8 / 16 that
+// rows per workgroup of ge2e_rows_contrast_kernel above GF_TILE speakers: the fewest of 4 / 8 / 16 that
 // put the Bl rows on the device in one round of workgroups (one per CU: the tile fills the LDS), 16
 // beyond that
 static int ct_rows_per_wg(int Bl, int cus) {
-  for (int rw = CT_ROWW; rw < 16; rw *= 2)
+  for (int rw = GF_ROWW; rw < 16; rw *= 2)
     if ((Bl + rw - 1) / rw <= cus) return rw;
   return 16;
 }
@@ -1114,14 +1052,14 @@ static bool rows_fuse_centroids(int N, int D) { return N > GF_TILE && N <= GF_NM
 static void launch_rows(int Bl, int M, int N, int D, int Np, int s0, const Ge2eWs& ws, const float* w, const float* b,
                         float* per, hipStream_t stream, const float* ssum = nullptr, int loss = SV_GE2E_SOFTMAX) {
   if (loss == SV_GE2E_CONTRAST) {  // one kernel for every fused shape; C^ always from ws.Chat
-    const int NT = N <= CT_TILE ? N : CT_TILE;
-    const int RW = N <= CT_TILE ? CT_ROWW : ct_rows_per_wg(Bl, sv_stream_cus(stream));
+    const int NT = N <= GF_TILE ? N : GF_TILE;
+    const int RW = N <= GF_TILE ? GF_ROWW : ct_rows_per_wg(Bl, sv_stream_cus(stream));
     const size_t lds = ((size_t)NT * (D + 4) + RW * (size_t)D) * sizeof(float);
     const dim3 grid((Bl + RW - 1) / RW), block(64 * RW);
 #define CT_LAUNCH(NH, RWV)                                                                                             \
   hipLaunchKernelGGL((ge2e_rows_contrast_kernel<NH, RWV>), grid, block, lds, stream, ws.Chat, ws.Ehat, ws.rawd, Bl, M, N, D, \
                      Np, s0, w, b, per, ws.cos, ws.dcos, ws.alpha, ws.dcd, ws.dwdb_rows, ws.G1)
-    if (N <= CT_TILE) CT_LAUNCH(2, CT_ROWW);
+    if (N <= GF_TILE) CT_LAUNCH(2, GF_ROWW);
     else if (RW == 4) CT_LAUNCH(4, 4);
     else if (RW == 8) CT_LAUNCH(4, 8);
     else CT_LAUNCH(4, 16);
@@ -1158,8 +1096,6 @@ static void launch_rows(int Bl, int M, int N, int D, int Np, int s0, const Ge2eW
 // order per (wave, sub-group), the sub-groups then the waves added in a fixed order.
 // (The sharded form, where beta_k and dC^_k go to the reduce buffer for the all-reduce and dE is
 // formed after it, is ge2e_cols_partial_kernel + ge2e_finalize_kernel.)
-#define GF_COLW 16
-#define GF_COLU 10
 __global__ __launch_bounds__(64 * GF_COLW) void ge2e_cols_kernel(int Bl, int M, int N, int D, int ldc,
                                                         const float* __restrict__ Chat, const float* __restrict__ Cn,
                                                         const float* __restrict__ Ehat, const float* __restrict__ Uhat,
@@ -1175,8 +1111,6 @@ __global__ __launch_bounds__(64 * GF_COLW) void ge2e_cols_kernel(int Bl, int M, 
   __shared__ float bpart[NW];
   __shared__ float dCs[64];
   __shared__ float dUs[GF_MMAX][64];
-  __shared__ float red2[2][NW];
-  __shared__ double redl[NW];
   const int k = blockIdx.x, q = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int s = lane >> 4, t = lane & 15;
@@ -1225,19 +1159,13 @@ __global__ __launch_bounds__(64 * GF_COLW) void ge2e_cols_kernel(int Bl, int M, 
     const int rr = k * M + w;
     rdx = (long)rr * D + d;
     const float un = Un[rr], en = En[rr], dd = dcd[rr];
-    const float iu = 1.0f / fmaxf(un, EPS_COS);
-    const float pu = un > EPS_COS ? 1.f : 0.f;
     const float eh = Ehat[rdx], uh = Uhat[rdx];
-    dU = dd * (eh - rawd[rr] * uh * pu) * iu;
-    const float ie = 1.0f / fmaxf(en, EPS_COS);
-    const float pe = en > EPS_COS ? 1.f : 0.f;
-    gE = (G1[rdx] + dd * uh - alpha[rr] * eh * pe) * ie;
+    dU = ge2e_dU(ge2e_norm(un), dd, eh, rawd[rr], uh);
+    gE = ge2e_gE(ge2e_norm(en), G1[rdx], dd, uh, alpha[rr], eh);
     dUs[w][lane] = dU;
   }
   __syncthreads();
-  const float cn = Cn[k];
-  const float icn = 1.0f / fmaxf(cn, EPS_COS);
-  const float pc = cn > EPS_COS ? 1.f : 0.f;
+  const Ge2eNorm cn = ge2e_norm(Cn[k]);
   float beta = 0.f;
 #pragma unroll
   for (int i = 0; i < NW; ++i) beta += bpart[i];
@@ -1245,45 +1173,15 @@ __global__ __launch_bounds__(64 * GF_COLW) void ge2e_cols_kernel(int Bl, int M, 
     float dch = 0.f;
 #pragma unroll
     for (int i = 0; i < NW; ++i) dch += part[i][tid];
-    dCs[tid] = (dch - beta * Chat[(long)k * D + d] * pc) * icn;
+    dCs[tid] = ge2e_dC(cn, dch, beta, Chat[(long)k * D + d]);
   }
   __syncthreads();
   if (mine) {
-    const float invM = 1.0f / (float)M, invm1 = 1.0f / (float)(M - 1);
     float sumdU = 0.f;
     for (int i = 0; i < M; ++i) sumdU += dUs[i][lane];
-    dE[rdx] = gE + dCs[lane] * invM + (sumdU - dU) * invm1;
+    dE[rdx] = ge2e_dE(gE, dCs[lane], sumdU, dU, M);
   }
-  if (k == 0 && q == 0) {  // loss = sum per, dw, db: fixed-order block sums (block-uniform branch)
-    double l = 0.0;  // the loss in fp64, rounded once (sum_kernel)
-    float a = 0.f, b = 0.f;
-    for (int i = tid; i < Bl; i += 64 * NW) {
-      l += (double)per[i];
-      a += dwdb_rows[i];
-      b += dwdb_rows[Bl + i];
-    }
-    l = wave_sum_d(l);
-    a = wave_sum(a);
-    b = wave_sum(b);
-    if (lane == 0) {
-      redl[w] = l;
-      red2[0][w] = a;
-      red2[1][w] = b;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      double s0 = 0.0;
-      float s1 = 0.f, s2 = 0.f;
-      for (int i = 0; i < NW; ++i) {
-        s0 += redl[i];
-        s1 += red2[0][i];
-        s2 += red2[1][i];
-      }
-      loss[0] = (float)s0;
-      dwdb[0] = s1;
-      dwdb[1] = s2;
-    }
-  }
+  if (k == 0 && q == 0) ge2e_loss_tail<NW>(per, dwdb_rows, Bl, loss, dwdb);  // (block-uniform branch)
 }
 
 // F3 in the sharded form for D <= 256 (the c4 / c5 ranks' small row counts): one workgroup per
@@ -1308,8 +1206,6 @@ __global__ __launch_bounds__(1024) void ge2e_cols_partial_kernel(int Bl, int N, 
   constexpr int NW = 16;
   __shared__ __attribute__((aligned(16))) float4 part[KB][NW][64];
   __shared__ float bpart[KB][NW];
-  __shared__ float red2[2][NW];
-  __shared__ double redl[NW];
   const int k0 = blockIdx.x * KB, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const bool dok = 4 * lane < D;
   float4 acc[KB];
@@ -1372,37 +1268,7 @@ __global__ __launch_bounds__(1024) void ge2e_cols_partial_kernel(int Bl, int N, 
       }
     }
   }
-  const int k = blockIdx.x;
-  if (k == 0) {  // loss = sum per, dw, db: fixed-order block sums (block-uniform branch)
-    double l = 0.0;  // the loss in fp64, rounded once (sum_kernel)
-    float a = 0.f, b = 0.f;
-    for (int i = tid; i < Bl; i += 64 * NW) {
-      l += (double)per[i];
-      a += dwdb_rows[i];
-      b += dwdb_rows[Bl + i];
-    }
-    l = wave_sum_d(l);
-    a = wave_sum(a);
-    b = wave_sum(b);
-    if (lane == 0) {
-      redl[w] = l;
-      red2[0][w] = a;
-      red2[1][w] = b;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      double s0 = 0.0;
-      float s1 = 0.f, s2 = 0.f;
-      for (int i = 0; i < NW; ++i) {
-        s0 += redl[i];
-        s1 += red2[0][i];
-        s2 += red2[1][i];
-      }
-      loss[0] = (float)s0;
-      dwdb[0] = s1;
-      dwdb[1] = s2;
-    }
-  }
+  if (blockIdx.x == 0) ge2e_loss_tail<NW>(per, dwdb_rows, Bl, loss, dwdb);  // (block-uniform branch)
 }
 
 // can the fused 3-launch path run this shape?
@@ -1414,8 +1280,7 @@ extern "C" int sv_ge2e_train_ok(int N, int M, int D) {
 // training step's): loss, per [N,M], dE [N,M,D], dwdb [2] = (dL/dw, dL/db)
 extern "C" int sv_ge2e_train_as(int loss_kind, const float* E, int N, int M, int D, const float* w, const float* b,
                                 float* loss, float* per, float* dE, float* dwdb, float* workspace, hipStream_t stream) {
-  if (!loss_known(loss_kind)) return SV_EARG;
-  if (!loss_shape_ok(loss_kind, N)) return SV_ESHAPE;
+  if (int rc = loss_args_check(loss_kind, N)) return rc;
   if (!E || !w || !b || !loss || !per || !dE || !dwdb || !workspace) return SV_EARG;
   if (!sv_ge2e_train_ok(N, M, D)) return SV_ESHAPE;
   if (((uintptr_t)E | (uintptr_t)workspace) & 15) return SV_EALIGN;
@@ -1461,8 +1326,7 @@ extern "C" int sv_ge2e_shard_prep(const float* E, int N_local, int M, int D, flo
 extern "C" int sv_ge2e_shard_rows_as(int loss, int N_local, int M, int D, int spk_offset, int N, const float* ssum_all,
                                      const float* w, const float* b, float* per, float* red, float* loss_local,
                                      float* dwdb_local, float* workspace, hipStream_t stream) {
-  if (!loss_known(loss)) return SV_EARG;
-  if (!loss_shape_ok(loss, N)) return SV_ESHAPE;
+  if (int rc = loss_args_check(loss, N)) return rc;
   if (!ssum_all || !w || !b || !per || !red || !loss_local || !dwdb_local || !workspace) return SV_EARG;
   if (!sv_ge2e_train_ok(N, M, D) || N_local <= 0 || spk_offset < 0 || spk_offset + N_local > N) return SV_ESHAPE;
   const Ge2eWs ws = carve(workspace, N_local, M, D, N);
@@ -1499,377 +1363,7 @@ extern "C" int sv_ge2e_shard_finalize(int N_local, int M, int D, int spk_offset,
   if (!red || !dE || !workspace || N_local <= 0 || M < 2 || D <= 0) return SV_EARG;
   const Ge2eWs ws = carve(workspace, N_local, M, D, N);
   const int Np = (N + 3) & ~3;
-  launch_finalize(N_local, M, D, spk_offset, red, red + (size_t)Np * D, ws, ws.dcd, dE, stream);
-  SV_LAUNCH_CHECK();
-  return SV_OK;
-}
-
-// ============================================================================
-// stand-alone forms of the reference helpers (utils.py): get_centroids, get_cossim
-// with arbitrary (e.g. enrollment) centroids, calc_loss on a given similarity matrix.
-// ============================================================================
-__global__ void ge2e_scale_kernel(float* __restrict__ x, long n, float s) {
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) x[i] *= s;
-}
-
-// cos[r, k] += 1e-6 for all k; cos[r, s(r)] = rawd[r] + 1e-6 when s(r) < Nc
-__global__ __launch_bounds__(256) void ge2e_cossim_fix_kernel(float* __restrict__ cos, const float* __restrict__ rawd,
-                                                              int Bl, int M, int Nc) {
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (r >= Bl) return;
-  const int j = r / M;
-  float* c = cos + (long)r * Nc;
-  for (int k = lane; k < Nc; k += 64) c[k] = (k == j ? rawd[r] : c[k]) + EPS_SIM;
-}
-
-// calc_loss (utils.py:126-132) on S [N, M, K]: per[j,i] = log(sum_k e^S + 1e-6) - S[j,i,j]
-__global__ __launch_bounds__(256) void ge2e_calc_loss_kernel(const float* __restrict__ S, int Bl, int M, int K,
-                                                             float* __restrict__ per) {
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (r >= Bl) return;
-  const float* s = S + (long)r * K;
-  float mx = -INFINITY;
-  for (int k = lane; k < K; k += 64) mx = fmaxf(mx, s[k]);
-  mx = fmaxf(wave_max(mx), 0.f);
-  float z = 0.f;
-  for (int k = lane; k < K; k += 64) z += expf(s[k] - mx);
-  z = wave_sum(z);
-  if (lane == 0) per[r] = mx + logf(z + EPS_LOG * expf(-mx)) - s[r / M];
-}
-
-extern "C" int sv_ge2e_centroids(const float* E, int N, int M, int D, float* C, hipStream_t stream) {
-  if (!E || !C || N <= 0 || M <= 0 || D <= 0) return SV_EARG;
-  hipLaunchKernelGGL(ge2e_sums_kernel, dim3(N), dim3(256), 0, stream, E, M, D, C);
-  SV_LAUNCH_CHECK();
-  const long n = (long)N * D;
-  hipLaunchKernelGGL(ge2e_scale_kernel, dim3((int)std::min<long>((n + 255) / 256, 1024)), dim3(256), 0, stream, C, n,
-                     1.0f / (float)M);
-  SV_LAUNCH_CHECK();
-  return SV_OK;
-}
-
-extern "C" size_t sv_ge2e_cossim_workspace(int N, int M, int D, int Nc) {
-  const size_t Bl = (size_t)N * M;
-  size_t n = al((size_t)N * D) + 2 * al(Bl * D) + 3 * al(Bl) + al((size_t)Nc * D) + al(Nc);
-  return n * sizeof(float) + sv_gemm_f32_workspace((int)Bl, Nc, D);
-}
-
-extern "C" int sv_ge2e_cossim(const float* E, int N, int M, int D, const float* C, int Nc, float* cos,
-                              float* workspace, hipStream_t stream) {
-  if (!E || !C || !cos || !workspace || N <= 0 || M < 2 || D <= 0 || D % 4 || Nc <= 0) return SV_EARG;
-  const int Bl = N * M;
-  float* p = workspace;
-  float* ssum = p; p += al((size_t)N * D);
-  float* Ehat = p; p += al((size_t)Bl * D);
-  float* Uhat = p; p += al((size_t)Bl * D);
-  float* En = p; p += al(Bl);
-  float* Un = p; p += al(Bl);
-  float* rawd = p; p += al(Bl);
-  float* Chat = p; p += al((size_t)Nc * D);
-  float* Cn = p; p += al(Nc);
-  float* gws = p;
-  hipLaunchKernelGGL(ge2e_sums_kernel, dim3(N), dim3(256), 0, stream, E, M, D, ssum);
-  SV_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ge2e_rowprep_kernel, dim3((Bl + 3) / 4), dim3(256), 0, stream, E, ssum, Bl, M, D, 0, Ehat, Uhat,
-                     En, Un, rawd);
-  SV_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ge2e_centroid_kernel, dim3(Nc), dim3(256), 0, stream, C, Nc, 1, D, Chat, Cn);
-  SV_LAUNCH_CHECK();
-  int rc = gemm_f32(1, 1, Bl, Nc, D, Ehat, D, Chat, D, cos, Nc, nullptr, nullptr, 0.f, gws, stream);
-  if (rc) return rc;
-  hipLaunchKernelGGL(ge2e_cossim_fix_kernel, dim3((Bl + 3) / 4), dim3(256), 0, stream, cos, rawd, Bl, M, Nc);
-  SV_LAUNCH_CHECK();
-  return SV_OK;
-}
-
-extern "C" int sv_ge2e_calc_loss(const float* S, int N, int M, int K, float* per, float* loss, hipStream_t stream) {
-  if (!S || !per || N <= 0 || M <= 0 || K < N) return SV_EARG;
-  const int Bl = N * M;
-  hipLaunchKernelGGL(ge2e_calc_loss_kernel, dim3((Bl + 3) / 4), dim3(256), 0, stream, S, Bl, M, K, per);
-  SV_LAUNCH_CHECK();
-  if (loss) {
-    hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(256), 0, stream, per, Bl, loss);
-    SV_LAUNCH_CHECK();
-  }
-  return SV_OK;
-}
-
-// calc_loss's contrast counterpart on S [N, M, K] (K >= N, at least one k != j)
-extern "C" int sv_ge2e_calc_contrast(const float* S, int N, int M, int K, float* per, float* loss, hipStream_t stream) {
-  if (!S || !per || N <= 0 || M <= 0 || K < N) return SV_EARG;
-  if (K < 2) return SV_ESHAPE;
-  const int Bl = N * M;
-  hipLaunchKernelGGL(ge2e_calc_contrast_kernel, dim3((Bl + 3) / 4), dim3(256), 0, stream, S, Bl, M, K, per);
-  SV_LAUNCH_CHECK();
-  if (loss) {
-    hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(256), 0, stream, per, Bl, loss);
-    SV_LAUNCH_CHECK();
-  }
-  return SV_OK;
-}
-
-extern "C" int sv_ge2e_calc_contrast_bwd(const float* S, int N, int M, int K, const float* gloss, const float* gper,
-                                         float* dS, hipStream_t stream) {
-  if (!S || !dS || N <= 0 || M <= 0 || K < N) return SV_EARG;
-  if (K < 2) return SV_ESHAPE;
-  const int Bl = N * M;
-  hipLaunchKernelGGL(ge2e_calc_contrast_bwd_kernel, dim3((Bl + 3) / 4), dim3(256), 0, stream, S, Bl, M, K, gloss, gper,
-                     dS);
-  SV_LAUNCH_CHECK();
-  return SV_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Backward passes of the stand-alone helpers (the autograd graphs of utils.py:28, :72-115,
-// :126-132), so a loss composed from them as in speech_embedder_net.py:45-48 trains.
-// ---------------------------------------------------------------------------
-// get_centroids: E.mean(1) -> dE[j,i,:] = dC[j,:] / M  (mean's backward divides by M)
-__global__ void ge2e_centroids_bwd_kernel(const float* __restrict__ dC, int N, int M, int D, float* __restrict__ dE) {
-  const long total = (long)N * M * D;
-  for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-    const int d = (int)(e % D);
-    const long j = e / ((long)M * D);
-    dE[e] = dC[j * D + d] / (float)M;
-  }
-}
-
-// get_cossim row pass, one wave per row r = (j, i): the upstream dcos row with the diagonal k = j
-// taken out (the index_put overwrote cos[j, :, j], so C_j gets nothing from it) -> dcoff, its
-// diagonal value -> dcd, the raw off-diagonal cosines (cosr, from the MFMA GEMM) with the
-// diagonal replaced by the leave-one-out one -> alpha_r = sum_k dcos[r,k] cos_raw[r,k]
-__global__ __launch_bounds__(256) void ge2e_cossim_bwd_rows_kernel(const float* __restrict__ dcos,
-                                                                   const float* __restrict__ cosr,
-                                                                   const float* __restrict__ rawd, int Bl, int M, int Nc,
-                                                                   int ldc, float* __restrict__ dcoff,
-                                                                   float* __restrict__ dcd, float* __restrict__ alpha) {
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (r >= Bl) return;
-  const int j = r / M;
-  const float* g = dcos + (long)r * Nc;
-  const float* c = cosr + (long)r * ldc;
-  float* o = dcoff + (long)r * ldc;
-  float a = 0.f;
-  for (int k = lane; k < ldc; k += 64) {
-    const float gk = k < Nc ? g[k] : 0.f;
-    a += gk * (k == j ? rawd[r] : c[k]);
-    o[k] = k == j ? 0.f : gk;
-  }
-  a = wave_sum(a);
-  if (lane == 0) {
-    alpha[r] = a;
-    dcd[r] = g[j];
-  }
-}
-
-// get_cossim, dE for one speaker per block (the finalize step without the centroid term):
-//   dU_r = dcd_r (E^_r - raw_r U^_r [|U|>eps]) / max(|U_r|, eps)
-//   dE_r = (G1_r + dcd_r U^_r - alpha_r E^_r [|E|>eps]) / max(|E_r|, eps) + (sum_i' dU_ji' - dU_r) / (M - 1)
-__global__ __launch_bounds__(256) void ge2e_cossim_bwd_de_kernel(
-    int M, int D, const float* __restrict__ Ehat, const float* __restrict__ Uhat, const float* __restrict__ En,
-    const float* __restrict__ Un, const float* __restrict__ rawd, const float* __restrict__ dcd,
-    const float* __restrict__ alpha, const float* __restrict__ G1, float* __restrict__ dE) {
-  const int j = blockIdx.x;
-  const float invm1 = 1.0f / (float)(M - 1);
-  for (int d = threadIdx.x; d < D; d += 256) {
-    float sumdU = 0.f;
-    for (int i = 0; i < M; ++i) {
-      const int r = j * M + i;
-      const float iu = 1.0f / fmaxf(Un[r], EPS_COS);
-      const float pu = Un[r] > EPS_COS ? 1.f : 0.f;
-      sumdU += dcd[r] * (Ehat[(long)r * D + d] - rawd[r] * Uhat[(long)r * D + d] * pu) * iu;
-    }
-    for (int i = 0; i < M; ++i) {
-      const int r = j * M + i;
-      const long rd = (long)r * D + d;
-      const float iu = 1.0f / fmaxf(Un[r], EPS_COS);
-      const float pu = Un[r] > EPS_COS ? 1.f : 0.f;
-      const float dU = dcd[r] * (Ehat[rd] - rawd[r] * Uhat[rd] * pu) * iu;
-      const float ie = 1.0f / fmaxf(En[r], EPS_COS);
-      const float pe = En[r] > EPS_COS ? 1.f : 0.f;
-      dE[rd] = (G1[rd] + dcd[r] * Uhat[rd] - alpha[r] * Ehat[rd] * pe) * ie + (sumdU - dU) * invm1;
-    }
-  }
-}
-
-// get_cossim, dC_k = (dChat_k - beta_k C^_k [|C|>eps]) / max(|C_k|, eps), one centroid per block
-__global__ __launch_bounds__(256) void ge2e_cossim_bwd_dc_kernel(int D, const float* __restrict__ dchat,
-                                                                 const float* __restrict__ beta,
-                                                                 const float* __restrict__ Chat,
-                                                                 const float* __restrict__ Cn, float* __restrict__ dC) {
-  const int k = blockIdx.x;
-  const float cn = Cn[k];
-  const float icn = 1.0f / fmaxf(cn, EPS_COS);
-  const float pc = cn > EPS_COS ? 1.f : 0.f;
-  for (int d = threadIdx.x; d < D; d += 256) {
-    const long cd = (long)k * D + d;
-    dC[cd] = (dchat[cd] - beta[k] * Chat[cd] * pc) * icn;
-  }
-}
-
-// calc_loss backward, one wave per row: dS_k = g_r (e^{S_k - mx} / (z + 1e-6 e^{-mx}) - [k == j]),
-// g_r = gloss + gper_r, with the forward's max shift (ge2e_calc_loss_kernel)
-__global__ __launch_bounds__(256) void ge2e_calc_loss_bwd_kernel(const float* __restrict__ S, int Bl, int M, int K,
-                                                                 const float* __restrict__ gloss,
-                                                                 const float* __restrict__ gper, float* __restrict__ dS) {
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (r >= Bl) return;
-  const int j = r / M;
-  const float* s = S + (long)r * K;
-  float mx = -INFINITY;
-  for (int k = lane; k < K; k += 64) mx = fmaxf(mx, s[k]);
-  mx = fmaxf(wave_max(mx), 0.f);
-  float z = 0.f;
-  for (int k = lane; k < K; k += 64) z += expf(s[k] - mx);
-  z = wave_sum(z);
-  const float inv = 1.0f / (z + EPS_LOG * expf(-mx));
-  const float g = (gloss ? *gloss : 0.f) + (gper ? gper[r] : 0.f);
-  for (int k = lane; k < K; k += 64) dS[(long)r * K + k] = g * (expf(s[k] - mx) * inv - (k == j ? 1.f : 0.f));
-}
-
-extern "C" int sv_ge2e_centroids_bwd(const float* dC, int N, int M, int D, float* dE, hipStream_t stream) {
-  if (!dC || !dE || N <= 0 || M <= 0 || D <= 0) return SV_EARG;
-  const long n = (long)N * M * D;
-  hipLaunchKernelGGL(ge2e_centroids_bwd_kernel, dim3((int)std::min<long>((n + 255) / 256, 4096)), dim3(256), 0, stream,
-                     dC, N, M, D, dE);
-  SV_LAUNCH_CHECK();
-  return SV_OK;
-}
-
-namespace {
-struct CosBwdWs {
-  float *ssum, *Ehat, *Uhat, *En, *Un, *rawd, *alpha, *dcd, *Chat, *Cn, *cosr, *dcoff, *G1, *dchat, *betap, *beta, *gemm;
-  size_t total;
-};
-CosBwdWs carve_cos_bwd(float* base, int N, int M, int D, int Nc) {
-  CosBwdWs w;
-  const size_t Bl = (size_t)N * M;
-  const int Ncp = (Nc + 3) & ~3;
-  size_t off = 0;
-  auto take = [&](size_t n) {
-    float* p = base ? base + off : nullptr;
-    off += al(n);
-    return p;
-  };
-  w.ssum = take((size_t)N * D);
-  w.Ehat = take(Bl * D);
-  w.Uhat = take(Bl * D);
-  w.En = take(Bl);
-  w.Un = take(Bl);
-  w.rawd = take(Bl);
-  w.alpha = take(Bl);
-  w.dcd = take(Bl);
-  w.Chat = take((size_t)Ncp * D);
-  w.Cn = take(Ncp);
-  w.cosr = take(Bl * Ncp);
-  w.dcoff = take(Bl * Ncp);
-  w.G1 = take(Bl * D);
-  w.dchat = take((size_t)Ncp * D);
-  w.betap = take(((Bl + 63) / 64) * (size_t)Ncp);
-  w.beta = take(Ncp);
-  size_t g = sv_gemm_f32_workspace((int)Bl, Ncp, D);
-  g = std::max(g, sv_gemm_f32_workspace((int)Bl, D, Ncp));
-  g = std::max(g, sv_gemm_f32_workspace(Ncp, D, (int)Bl));
-  w.gemm = take((g + 3) / 4);
-  w.total = off * sizeof(float);
-  return w;
-}
-}  // namespace
-
-extern "C" size_t sv_ge2e_cossim_bwd_workspace(int N, int M, int D, int Nc) {
-  return carve_cos_bwd(nullptr, N, M, D, Nc).total;
-}
-
-extern "C" int sv_ge2e_cossim_bwd(const float* E, int N, int M, int D, const float* C, int Nc, const float* dcos,
-                                  float* dE, float* dC, float* workspace, hipStream_t stream) {
-  if (!E || !C || !dcos || !dE || !dC || !workspace || N <= 0 || M < 2 || D <= 0 || D % 4 || Nc < N) return SV_EARG;
-  const int Bl = N * M, Ncp = (Nc + 3) & ~3;
-  const CosBwdWs ws = carve_cos_bwd(workspace, N, M, D, Nc);
-  hipLaunchKernelGGL(ge2e_sums_kernel, dim3(N), dim3(256), 0, stream, E, M, D, ws.ssum);
-  SV_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ge2e_rowprep_kernel, dim3((Bl + 3) / 4), dim3(256), 0, stream, E, ws.ssum, Bl, M, D, 0, ws.Ehat,
-                     ws.Uhat, ws.En, ws.Un, ws.rawd);
-  SV_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ge2e_centroid_kernel, dim3(Ncp), dim3(256), 0, stream, C, Nc, 1, D, ws.Chat, ws.Cn);
-  SV_LAUNCH_CHECK();
-  // the raw cosines E^ C^T (padding columns zero)
-  int rc = gemm_f32(1, 1, Bl, Ncp, D, ws.Ehat, D, ws.Chat, D, ws.cosr, Ncp, nullptr, nullptr, 0.f, ws.gemm, stream);
-  if (rc) return rc;
-  hipLaunchKernelGGL(ge2e_cossim_bwd_rows_kernel, dim3((Bl + 3) / 4), dim3(256), 0, stream, dcos, ws.cosr, ws.rawd, Bl,
-                     M, Nc, Ncp, ws.dcoff, ws.dcd, ws.alpha);
-  SV_LAUNCH_CHECK();
-  // G1 = dcoff C^ ([Bl, Ncp] x [Ncp, D]);  dChat = dcoff^T E^ ([Ncp, Bl] x [Bl, D])
-  rc = gemm_f32(1, 0, Bl, D, Ncp, ws.dcoff, Ncp, ws.Chat, D, ws.G1, D, nullptr, nullptr, 0.f, ws.gemm, stream);
-  if (rc) return rc;
-  rc = gemm_f32(0, 0, Ncp, D, Bl, ws.dcoff, Ncp, ws.Ehat, D, ws.dchat, D, nullptr, nullptr, 0.f, ws.gemm, stream);
-  if (rc) return rc;
-  const int nchunk = (Bl + 63) / 64;
-  hipLaunchKernelGGL(ge2e_beta_partial_kernel, dim3((Nc + 63) / 64, nchunk), dim3(256), 0, stream, ws.dcoff, ws.cosr,
-                     Bl, Nc, Ncp, ws.betap);
-  SV_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ge2e_beta_final_kernel, dim3((Nc + 255) / 256), dim3(256), 0, stream, ws.betap, nchunk, Nc,
-                     ws.beta);
-  SV_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ge2e_cossim_bwd_de_kernel, dim3(N), dim3(256), 0, stream, M, D, ws.Ehat, ws.Uhat, ws.En, ws.Un,
-                     ws.rawd, ws.dcd, ws.alpha, ws.G1, dE);
-  SV_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ge2e_cossim_bwd_dc_kernel, dim3(Nc), dim3(256), 0, stream, D, ws.dchat, ws.beta, ws.Chat, ws.Cn,
-                     dC);
-  SV_LAUNCH_CHECK();
-  return SV_OK;
-}
-
-extern "C" int sv_ge2e_calc_loss_bwd(const float* S, int N, int M, int K, const float* gloss, const float* gper,
-                                     float* dS, hipStream_t stream) {
-  if (!S || !dS || N <= 0 || M <= 0 || K < N) return SV_EARG;
-  const int Bl = N * M;
-  hipLaunchKernelGGL(ge2e_calc_loss_bwd_kernel, dim3((Bl + 3) / 4), dim3(256), 0, stream, S, Bl, M, K, gloss, gper, dS);
-  SV_LAUNCH_CHECK();
-  return SV_OK;
-}
-
-// ============================================================================
-// EER threshold sweep (train_speech_embedder.py:134-149): for each threshold, the number of
-// similarities above it (all entries and the diagonal k == j).  One block per threshold;
-// integer counts, so the result is exact.
-// ============================================================================
-__global__ __launch_bounds__(256) void eer_counts_kernel(const float* __restrict__ S, int N, int M2, int Nc,
-                                                         const float* __restrict__ thr, float* __restrict__ cnt_all,
-                                                         float* __restrict__ cnt_diag) {
-  __shared__ int red[2][4];
-  const float th = thr[blockIdx.x];
-  const long total = (long)N * M2 * Nc;
-  int a = 0, d = 0;
-  for (long e = threadIdx.x; e < total; e += 256) {
-    const int k = (int)(e % Nc);
-    const int j = (int)(e / ((long)M2 * Nc));
-    const int over = S[e] > th;
-    a += over;
-    d += (over && k == j);
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    a += __shfl_xor(a, o, 64);
-    d += __shfl_xor(d, o, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = a;
-    red[1][threadIdx.x >> 6] = d;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    cnt_all[blockIdx.x] = (float)(red[0][0] + red[0][1] + red[0][2] + red[0][3]);
-    cnt_diag[blockIdx.x] = (float)(red[1][0] + red[1][1] + red[1][2] + red[1][3]);
-  }
-}
-
-extern "C" int sv_eer_counts(const float* S, int N, int M2, int Nc, const float* thresholds, int n_thr,
-                             float* cnt_all, float* cnt_diag, hipStream_t stream) {
-  if (!S || !thresholds || !cnt_all || !cnt_diag || N <= 0 || M2 <= 0 || Nc < N || n_thr <= 0) return SV_EARG;
-  hipLaunchKernelGGL(eer_counts_kernel, dim3(n_thr), dim3(256), 0, stream, S, N, M2, Nc, thresholds, cnt_all, cnt_diag);
+  launch_finalize(N_local, M, D, spk_offset, red, red + (size_t)Np * D, ws, dE, stream);
   SV_LAUNCH_CHECK();
   return SV_OK;
 }

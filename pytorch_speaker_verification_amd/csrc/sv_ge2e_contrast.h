@@ -1,8 +1,11 @@
-// GE2E contrast loss (arXiv 1710.10467 eq. 7): the row step of csrc/sv_ge2e.hip for
+// GE2E contrast loss (arXiv 1710.10467 eq. 7):
 //   per_r = 1 - sigma(S[r, s(r)]) + max_{k != s(r)} sigma(S[r, k]),   loss = sum per
-// on the same cos and S = w (cos + 1e-6) + b as the softmax loss.  Included by sv_ge2e.hip only (it
-// uses that file's EPS_* constants); every kernel around the row step -- prep, centroids, the cosine and
-// Jacobian GEMMs, beta, cols, finalize -- is the softmax path's, unchanged.
+// on the same cos and S = w (cos + 1e-6) + b as the softmax loss.  This header holds the loss's row
+// arithmetic (inline device functions) and its fused row kernel (a template), so any translation
+// unit may include it: sv_ge2e.hip launches the fused kernel and defines the split path's row
+// kernels on this arithmetic, sv_ge2e_utils.hip the stand-alone calc_contrast helpers.  Every
+// kernel around the row step -- prep, centroids, the cosine and Jacobian GEMMs, beta, cols,
+// finalize -- is the softmax path's, unchanged.
 //
 // sigma is monotone, so the maximum sits where S is largest over k != s(r) (a negative w selects the
 // smallest cosine); ties go to the lowest k, torch.max(dim)'s index.  With p = sigma(S_d) on the
@@ -12,9 +15,7 @@
 // scaled centroid row.
 #pragma once
 #include <limits.h>
-
-constexpr int CT_ROWW = 4;    // rows (waves) per workgroup of the fused row step: 4, or 8 / 16 above CT_TILE speakers
-constexpr int CT_TILE = 128;  // speakers per LDS tile of C^ (133 KB of fp32 at D = 256)
+#include "sv_ge2e_dev.h"
 
 // sigma(x) from e = e^{-|x|} in (0, 1]: e / (1 + e) below 0 (no overflow, the small tail kept: at
 // S = -14 it is 8.3e-7 to fp32 relative precision, where 1 - 1 / (1 + e^14) would keep 3 digits)
@@ -63,17 +64,33 @@ __device__ __forceinline__ CtRow ct_row(float wv, float bv, float g, float cd, f
   return o;
 }
 
+// k* of a row of a given S [K] whose positive is column j: the maximum runs over every k != j, k < K
+// (the stand-alone helpers; bs: the maximum itself)
+__device__ __forceinline__ int ct_row_argmax(const float* __restrict__ s, int K, int j, int lane, float& bs) {
+  bs = -INFINITY;
+  int bk = INT_MAX;
+  for (int k = lane; k < K; k += 64) {
+    const float v = s[k];
+    if (k != j && v > bs) {
+      bs = v;
+      bk = k;
+    }
+  }
+  ct_wave_argmax(bs, bk);
+  return ct_legal(bk, K, j);
+}
+
 // F2 of the fused path for the contrast loss, local and sharded (s0 > 0, C^ from
 // ge2e_centroid_kernel) alike, over the whole sv_ge2e_train_ok domain.  The frame is
-// ge2e_rows_kernel's: RW rows per workgroup, one wave per row, C^ staged in LDS as
-// Cs [NT][D + 4] (one tile up to CT_TILE speakers, NH = 2; two tiles of CT_TILE above, NH = 4), the
-// cosines with lanes over speakers and E^ broadcast.  What follows differs: no exponent sum and no
+// ge2e_rows_kernel's, from sv_ge2e_dev.h: RW rows per workgroup, one wave per row, C^ staged in LDS
+// (one tile up to GF_TILE speakers, NH = 2; two tiles above, NH = 4), the cosines with lanes over
+// speakers and E^ broadcast.  What follows differs: no exponent sum and no
 // pass over the tiles for G1.  Each lane keeps the best (S, k) of its off-diagonal speakers across
 // the tiles, one wave arg max picks k*, and G1_r = dcos_k* C^_k* reads that one centroid row from
 // global memory (1 KB, L2 resident), so tile 0 is never staged a second time.  Writes exactly what
 // ge2e_rows_kernel hands to F1 / F3: per, the cos row, a dense dcos row [ldc] (zero outside k*, the
 // padding columns N .. ldc - 1 included), alpha, dcd, dwdb_rows and G1.
-// RW (the launcher's choice, ct_rows_per_wg): above CT_TILE speakers the kernel is bound by the
+// RW (the launcher's choice, ct_rows_per_wg): above GF_TILE speakers the kernel is bound by the
 // staging, 266 KB from L2 per WORKGROUP whatever its row count, so a workgroup should carry as many
 // rows as still leaves one workgroup per CU.  Measured at (256, 10, 256), 2560 rows on 256 CUs, the
 // whole three-launch step: RW = 4 (640 workgroups, three rounds) 113.4 us, RW = 8 (320) 102.8,
@@ -87,74 +104,21 @@ __global__ __launch_bounds__(64 * RW) void ge2e_rows_contrast_kernel(
   static_assert(NH == 2 || NH == 4, "NH: 64-speaker groups per lane");
   extern __shared__ __attribute__((aligned(16))) float gsm[];
   const int LDC = D + 4;
-  const int NT = NH == 2 ? N : CT_TILE;  // speakers per LDS tile
+  const int NT = NH == 2 ? N : GF_TILE;  // speakers per LDS tile
   float* Cs = gsm;                       // [NT][LDC]
   float* Es = Cs + (size_t)NT * LDC;     // [RW][D]
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int D4 = D / 4;
-  // C^ rows k0 .. into LDS: by LDS-DMA at D = 256 (a 1 KB row per wave instruction), else through
-  // registers; the caller waits (vmcnt(0) + barrier)
-  auto stage = [&](int k0) {
-    const int nk = min(NT, N - k0);
-    if (D == 256) {
-      for (int row = w; row < nk; row += RW)
-        __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)(Chat + (long)(k0 + row) * D + lane * 4),
-                                         (__attribute__((address_space(3))) void*)(Cs + row * LDC), 16, 0, 0);
-      return;
-    }
-    const int NQ = nk * D4;
-#pragma unroll 8
-    for (int q = tid; q < NQ; q += 64 * RW) {
-      const int row = q / D4, col = (q - row * D4) * 4;
-      *reinterpret_cast<float4*>(Cs + row * LDC + col) =
-          *reinterpret_cast<const float4*>(Chat + (long)(k0 + row) * D + col);
-    }
-  };
-  stage(0);
+  ge2e_stage_tile<RW>(Chat, Cs, 0, NT, N, D);
   const int r = blockIdx.x * RW + w;  // this wave's row
   const bool live = r < Bl;
   if (live)
     for (int c = lane * 4; c < D; c += 256)
       *reinterpret_cast<float4*>(Es + w * D + c) = *reinterpret_cast<const float4*>(Ehat + (long)r * D + c);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's LDS-DMA of C^ landed
   __syncthreads();
-  // cosines: KS speaker lanes x DS d-slices as in ge2e_rows_kernel (small N splits D so that every
-  // lane works; the slices meet by a butterfly); speaker lane + 64 h is cv[h]
-  int DS = N <= 8 ? 8 : N <= 16 ? 4 : N <= 32 ? 2 : 1;
-  while (DS > 1 && D % (4 * DS)) DS >>= 1;
-  const int KS = 64 / DS, dlen = D / DS;
-  const int kl = lane & (KS - 1), d0 = (lane / KS) * dlen;
   float cv[NH];
-#pragma unroll
-  for (int h = 0; h < NH; ++h) cv[h] = 0.f;
-  const float* e0 = Es + w * D;
-#pragma unroll
-  for (int t = 0; t < NH / 2; ++t) {
-    if (t > 0) {  // NH == 4: the second tile (every wave of the workgroup, live or not)
-      __syncthreads();
-      stage(t * CT_TILE);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-    }
-#pragma unroll
-    for (int hk = 0; hk < 2; ++hk) {
-      const int kt = kl + 64 * hk;  // speaker within the tile
-      if (live && t * CT_TILE + kt < N) {
-        float4 a = float4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 8
-        for (int c = d0; c < d0 + dlen; c += 4) {
-          const float4 cc = *reinterpret_cast<const float4*>(Cs + kt * LDC + c);
-          const float4 x0 = *reinterpret_cast<const float4*>(e0 + c);
-          a.x += x0.x * cc.x;
-          a.y += x0.y * cc.y;
-          a.z += x0.z * cc.z;
-          a.w += x0.w * cc.w;
-        }
-        cv[2 * t + hk] = (a.x + a.y) + (a.z + a.w);
-      }
-    }
-  }
-  if (!live) return;  // (no workgroup barrier below)
+  const int KS = ge2e_cos_step<NH, RW>(Chat, Cs, Es + w * D, live, NT, N, D, cv);
+  if (!live) return;  // (no workgroup barrier below; the second tile's are above, for every wave)
   for (int o = KS; o < 64; o <<= 1) cv[0] += __shfl_xor(cv[0], o, 64);  // lane k < KS: speaker k
   const float wv = *wp, bv = *bp;
   const int sg = s0 + r / M;  // global speaker of this row
@@ -200,116 +164,4 @@ __global__ __launch_bounds__(64 * RW) void ge2e_rows_contrast_kernel(
     const float4 cc = *reinterpret_cast<const float4*>(Chat + (long)bk * D + c);
     *reinterpret_cast<float4*>(G1 + (long)r * D + c) = float4{o.dck * cc.x, o.dck * cc.y, o.dck * cc.z, o.dck * cc.w};
   }
-}
-
-// ---- split path: the contrast counterparts of ge2e_rowloss_kernel / ge2e_rowbwd_kernel /
-// ge2e_dcd_kernel on the GEMM-formed cos [Bl, ldc].  One wave per row.  The forward leaves k* (as
-// integer bits) in the workspace slot that holds logz for the softmax; the backward reads it back, so
-// both pick the same column by construction.
-__global__ __launch_bounds__(256) void ge2e_rowloss_contrast_kernel(float* __restrict__ cos, const float* __restrict__ rawd,
-                                                                    int Bl, int M, int N, int ldc, int s0,
-                                                                    const float* __restrict__ wp,
-                                                                    const float* __restrict__ bp, float* __restrict__ per,
-                                                                    float* __restrict__ kst) {
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (r >= Bl) return;
-  const int sg = s0 + r / M;
-  const float w = *wp, b = *bp;
-  float* c = cos + (long)r * ldc;
-  const float rd = rawd[r];
-  if (lane == 0) c[sg] = rd;  // get_cossim's diagonal overwrite (no lane reads c[sg] below)
-  float bs = -INFINITY;
-  int bk = INT_MAX;
-  for (int k = lane; k < N; k += 64) {
-    const float s = w * (c[k] + EPS_SIM) + b;
-    if (k != sg && s > bs) {
-      bs = s;
-      bk = k;
-    }
-  }
-  ct_wave_argmax(bs, bk);
-  bk = ct_legal(bk, N, sg);
-  if (lane == 0) {
-    per[r] = ct_row(w, b, 1.0f, rd, c[bk]).per;
-    kst[r] = __int_as_float(bk);
-  }
-}
-
-__global__ __launch_bounds__(256) void ge2e_rowbwd_contrast_kernel(const float* __restrict__ cos, const float* __restrict__ kst,
-                                                                   int Bl, int M, int N, int ldc, int s0,
-                                                                   const float* __restrict__ wp,
-                                                                   const float* __restrict__ bp, const float* __restrict__ gl,
-                                                                   float* __restrict__ dcos, float* __restrict__ alpha,
-                                                                   float* __restrict__ dwdb) {
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (r >= Bl) return;
-  const int sg = s0 + r / M;
-  const float g = gl ? *gl : 1.0f;
-  const float* c = cos + (long)r * ldc;
-  const int bk = ct_legal(__float_as_int(kst[r]), N, sg);
-  const CtRow o = ct_row(*wp, *bp, g, c[sg], c[bk]);
-  float* dc = dcos + (long)r * ldc;
-  for (int k = lane; k < ldc; k += 64) dc[k] = (k == bk) ? o.dck : 0.f;
-  if (lane == 0) {
-    alpha[r] = o.alpha;
-    dwdb[r] = o.dw;
-    dwdb[Bl + r] = o.db;
-  }
-}
-
-// dcos on the diagonal, w g dS[r, s(r)] = -w g p (1 - p), for the finalize step
-__global__ void ge2e_dcd_contrast_kernel(const float* __restrict__ rawd, int Bl, const float* __restrict__ wp,
-                                         const float* __restrict__ bp, const float* __restrict__ gl,
-                                         float* __restrict__ dcd) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= Bl) return;
-  const float w = *wp, g = gl ? *gl : 1.0f;
-  dcd[r] = -w * g * ct_dsigmoid(w * (rawd[r] + EPS_SIM) + *bp);
-}
-
-// ---- stand-alone helper on a given S [N, M, K], K >= N: the positive is column j, the maximum runs
-// over every k != j, k < K
-__device__ __forceinline__ int ct_row_argmax(const float* __restrict__ s, int K, int j, int lane, float& bs) {
-  bs = -INFINITY;
-  int bk = INT_MAX;
-  for (int k = lane; k < K; k += 64) {
-    const float v = s[k];
-    if (k != j && v > bs) {
-      bs = v;
-      bk = k;
-    }
-  }
-  ct_wave_argmax(bs, bk);
-  return ct_legal(bk, K, j);
-}
-
-__global__ __launch_bounds__(256) void ge2e_calc_contrast_kernel(const float* __restrict__ S, int Bl, int M, int K,
-                                                                 float* __restrict__ per) {
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (r >= Bl) return;
-  const float* s = S + (long)r * K;
-  const int j = r / M;
-  float bs;
-  const int bk = ct_row_argmax(s, K, j, lane, bs);
-  if (lane == 0) per[r] = ct_sigmoid(-s[j]) + ct_sigmoid(s[bk]);
-}
-
-// dS_j = -g_r p (1 - p), dS_k* = g_r q (1 - q), 0 elsewhere; g_r = gloss + gper_r
-__global__ __launch_bounds__(256) void ge2e_calc_contrast_bwd_kernel(const float* __restrict__ S, int Bl, int M, int K,
-                                                                     const float* __restrict__ gloss,
-                                                                     const float* __restrict__ gper,
-                                                                     float* __restrict__ dS) {
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (r >= Bl) return;
-  const float* s = S + (long)r * K;
-  const int j = r / M;
-  float bs;
-  const int bk = ct_row_argmax(s, K, j, lane, bs);
-  const float g = (gloss ? *gloss : 0.f) + (gper ? gper[r] : 0.f);
-  const float dj = -g * ct_dsigmoid(s[j]), dk = g * ct_dsigmoid(s[bk]);
-  for (int k = lane; k < K; k += 64) dS[(long)r * K + k] = k == j ? dj : k == bk ? dk : 0.f;
 }

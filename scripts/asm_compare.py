@@ -6,9 +6,13 @@
 Made with `hipcc <the Makefile's flags> --cuda-device-only -S` (and --cuda-host-only) per source
 file.  Each function's body (device: kernel code + its .amdhsa_kernel descriptor; host: the x86
 text) is normalised for label numbering and compared; prints the functions that differ, exist in
-one build only, and a summary.  Used to show that a source clean-up (dead A/B branches removed)
-leaves every kept kernel's and host function's code unchanged.
+one build only, and a summary.  Under a function that differs: the opcodes whose counts differ and
+the .amdhsa_* descriptor lines that differ (registers, scratch, LDS), A -> B.  Used to show that a
+source clean-up leaves every kept kernel's and host function's code unchanged, and what moved in a
+kernel whose source was refactored.  A translation unit split in two is compared by concatenating
+the two .s files of that build under the old name.
 """
+import collections
 import os
 import re
 import sys
@@ -68,6 +72,26 @@ def norm(body):
     return res
 
 
+def report(na, nb):
+    """What differs between two normalised bodies of one function: the opcodes whose counts differ
+    (count in A -> count in B) and the .amdhsa_* descriptor lines that differ."""
+    def parts(body):
+        cut = body.index("#desc") if "#desc" in body else len(body)
+        ops = collections.Counter(ln.split()[0] for ln in body[:cut] if not ln.rstrip().endswith(":")
+                                  and not ln.lstrip().startswith("."))
+        desc = dict(ln.split(None, 1) for ln in body[cut + 1:] if ln.lstrip().startswith(".amdhsa_"))
+        return ops, desc
+    (oa, da), (ob, db) = parts(na), parts(nb)
+    for op in sorted(set(oa) | set(ob)):
+        if oa[op] != ob[op]:
+            print(f"    {op:<28} {oa[op]:>5} -> {ob[op]:<5}")
+    if oa == ob:
+        print("    (the same opcode counts: registers, order or operands differ)")
+    for k in sorted(set(da) | set(db)):
+        if da.get(k) != db.get(k):
+            print(f"    {k:<52} {da.get(k, '-')} -> {db.get(k, '-')}")
+
+
 def main(a, b):
     same = diff = only_a = only_b = 0
     for fn in sorted(os.listdir(a)):
@@ -84,6 +108,7 @@ def main(a, b):
             elif norm(fa[k]) != norm(fb[k]):
                 diff += 1
                 print(f"DIFFERENT  {fn}: {k}")
+                report(norm(fa[k]), norm(fb[k]))
             else:
                 same += 1
     print(f"identical {same}, different {diff}, only in A {only_a}, only in B {only_b}")

@@ -47,7 +47,7 @@ GAP_FLOOR = 1e-4
 # seeds moved where the first draw's top-two gap fell below GAP_FLOOR
 SEED_SHIFT = {(129, 11, 256): 2, (255, 2, 256): 1, (129, 16, 256): 9}
 
-# one shape beyond ge2e_cases' table: 2064 rows above CT_TILE speakers, where the contrast rows kernel
+# one shape beyond ge2e_cases' table: 2064 rows above GF_TILE speakers, where the contrast rows kernel
 # runs 16 rows per workgroup on a 256-CU device (csrc/sv_ge2e.hip ct_rows_per_wg; the table's own
 # shapes reach 4 and 8).  Its reference is contrast_per_mm's (the broadcast form would take 4 GB);
 # first seed shift with a gap above the floor: 9 (7.1e-4).  It is part of the PORT_MAX table.
