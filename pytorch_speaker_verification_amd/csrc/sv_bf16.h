@@ -430,6 +430,7 @@ __device__ __forceinline__ void lstm_cell_bwd_x4(const V4& dh, const A4& i, cons
 #define SV_NSTAMP_WG 1024
 #define SV_SYNC_STAMP (SV_SYNC_CNT + SV_SYNC_CHANNELS * SV_PCNT_ROWS * SV_PCNT_STRIDE)
 #define SV_SYNC_WORDS (SV_SYNC_STAMP + 2 * SV_NSTAMP_WG * SV_NSTAMP)
+unsigned* sv_sync_cnt(unsigned* sync, int chan);  // counter channel `chan` of a sync block (sv_sync.hip)
 
 // persistent forward recurrence of one layer (sv_persist.hip); sync: the caller's block, chan: its
 // counter channel
@@ -478,7 +479,7 @@ __device__ __forceinline__ void dbfin_run(const DbFin& f, int blk) {
   o1[c] = s;
   if (o2) o2[c] = s;
 }
-int sv_dbfin_launch(const DbFin& f, hipStream_t stream);  // as its own launch (sv_persist.hip)
+int sv_dbfin_launch(const DbFin& f, hipStream_t stream);  // as its own launch (sv_sync.hip)
 // launcher of the wide-tile persistent backward (sv_persist3.hip; grid = nub x nrb workgroups)
 int sv_persist3_bwd_launch(dim3 grid, int nub, hipStream_t stream, const bf16_t* whhT, const bf16_t* acts,
                            const float* c_tm, const float* dhup, int up_full, bf16_t* dg, bf16_t* dgT, long lddgT,

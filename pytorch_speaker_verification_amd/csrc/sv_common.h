@@ -49,9 +49,9 @@ int gemm_f32_dx_afrag(int bn, const float* dgf, int T, int B, int H, const float
 // fp32 W-stationary persistent recurrences of one layer (sv_persist_f32.hip): H = 768, 64-row x
 // 32-unit tiles co-resident on `cus` CUs; dgf: sv_persist_f32_bwd_scratch bytes (16-B aligned)
 int sv_persist_f32_fits(int B, int H, int cus);
-int sv_stream_cus(hipStream_t stream);  // CUs of the stream's device (sv_persist.hip)
+int sv_stream_cus(hipStream_t stream);  // CUs of the stream's device (sv_sync.hip)
 // zero `words` arrival-counter words in each of `nchan` channels (channel c at cnt + c * chan_stride)
-// with ONE kernel on `stream` (sv_persist.hip).  Never hipMemsetAsync for the counters: replayed
+// with ONE kernel on `stream` (sv_sync.hip).  Never hipMemsetAsync for the counters: replayed
 // from a HIP graph, a memset node's reset was not reliably seen by the persistent kernel's
 // agent-scope atomics and polls (scripts/f32_replay_diag.py)
 int sv_zero_counters(unsigned* cnt, int nchan, long chan_stride, int words, hipStream_t stream);

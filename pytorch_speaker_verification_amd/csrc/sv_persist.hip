@@ -28,6 +28,7 @@
 #include "../../include/sv_ge2e.h"
 
 #include "sv_persist_dev.h"
+#include "sv_persist_plan.h"
 
 // A-operand tile of a handed-off buffer: [R][BK] bf16 rows (row stride ld elements) read with
 // buffer_load_dwordx4 sc1 (bypasses the CU's L1, L2-served; rows past the buffer end read 0)
@@ -103,6 +104,15 @@ __device__ __forceinline__ void persist_mainloop(__amdgpu_buffer_rsrc_t ra, int 
 //   c_tm [T,B,H], h_tm [T+1,B,H] (slot 0 = 0), h_bf [T+1,B,H] (slot 0 = 0, the hand-off),
 //   hT [H,(T+1)Bp] or NULL.  cnt: this launch's zeroed row-block counters.
 // ============================================================================
+// its LDS: the main loop's two k-tile buffers ([BF_BM + BN][BBK + 8] bf16 each); the epilogue
+// reuses them as pre [BF_BM][LDP] fp32 | hs [BF_U][LDH] fp32
+struct PFwdLds {
+  static constexpr int BN = 4 * BF_U, LDP = BN + 4, LDH = BF_BM + 1;
+  static constexpr int main_bytes = 2 * (BF_BM + BN) * (BBK + 8) * 2;
+  static constexpr int pre = 0, hs = pre + BF_BM * LDP * 4, epi_bytes = hs + BF_U * LDH * 4;
+  static constexpr int bytes = main_bytes > epi_bytes ? main_bytes : epi_bytes;
+  static_assert(bytes <= SV_LDS_BYTES, "LDS of a CU");
+};
 template <int D>
 __global__ __launch_bounds__(512) void lstm_persist_fwd_bf16_kernel(const bf16_t* __restrict__ whh_bf,
                                                                     bf16_t* __restrict__ gates,
@@ -114,7 +124,7 @@ __global__ __launch_bounds__(512) void lstm_persist_fwd_bf16_kernel(const bf16_t
                                                                     int dbg) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16_t* ldsb = reinterpret_cast<bf16_t*>(smem);
-  constexpr int BN = 4 * BF_U, LDP = BN + 4, LDH = BF_BM + 1;
+  constexpr int BN = PFwdLds::BN, LDP = PFwdLds::LDP, LDH = PFwdLds::LDH;
   constexpr int PER = BF_BM * BF_U / 512;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int j0 = blockIdx.x * BF_U, b0 = blockIdx.y * BF_BM;
@@ -125,8 +135,8 @@ __global__ __launch_bounds__(512) void lstm_persist_fwd_bf16_kernel(const bf16_t
   float cst[PER];
 #pragma unroll
   for (int k = 0; k < PER; ++k) cst[k] = 0.f;
-  float* pre = reinterpret_cast<float*>(smem);
-  float* hs = pre + BF_BM * LDP;
+  float* pre = reinterpret_cast<float*>(smem + PFwdLds::pre);
+  float* hs = reinterpret_cast<float*>(smem + PFwdLds::hs);
   for (int t = 0; t < T; ++t) {
     bf16_t* gt = gates + (long)t * B * G;
     float xg[PER][4];
@@ -194,29 +204,34 @@ __global__ __launch_bounds__(512) void lstm_persist_fwd_bf16_kernel(const bf16_t
       }
     }
     // publish: every wave drains its stores, barrier, one lane arrives on the row block
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0 && persist_arrive_ok(fault, t == 0))
-      __hip_atomic_fetch_add(my_cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    persist_publish(my_cnt, fault, t == 0);
   }
 }
 
 // ============================================================================
-// W-stationary variant (H = 16 NS): 4 waves, wave g owns gate g of the tile's 32 units for all
-// 64 rows (two 32x32 accumulators) and keeps its W_hh rows -- 32 x H bf16, the MFMA B
+// W-stationary variant (H = 16 NS): 4 waves, wave g owns gate g of the tile's 32 units for the
+// tile's 32 rows (one 32x32 accumulator) and keeps its W_hh rows -- 32 x H bf16, the MFMA B
 // fragments of every k-step -- in registers for the whole sequence.  Per step only h_{t-1}
-// (64 rows x H) is staged into LDS (two halves of sc1 buffer loads); each wave reads it as A
+// (32 rows x H) is staged into LDS (two halves of sc1 buffer loads); each wave reads it as A
 // fragments: 1 LDS fragment per MFMA instead of 2, no W traffic at all after the prologue.
-// Epilogue: each thread owns 4 consecutive units of 2 rows (16-B operand loads and stores);
+// Epilogue: each thread owns 4 consecutive units of one row (16-B operand loads and stores);
 // only the h_bf hand-off (16-B sc1 stores from an LDS-staged tile) precedes the arrival, the
 // activations, c, h and hT (16-B transposed chunks) are stored after it.
+// (The 64-row form of this tile is gone: at H = 768 no device below 792 CUs selects it)
 // ============================================================================
 // XF > 0 (layer 0, F = 8 * XF <= 48 input features): the input projection x_t W_ih^T + b_ih + b_hh
 // is computed in the kernel from x_bf [T,B,F] and W_ih [4H,F] (held in registers beside W_hh:
 // 3 k-steps of 16, zero-padded), so the layer needs no K1 GEMM and its step loads 80 B per row
 // instead of 4 x 4H fp32 pre-activations; the sum (MFMA over the zero-padded k range, then the
 // two biases, rounded to bf16 as the K1 GEMM stores it) matches the K1 path bit for bit.
-template <int NS, int BM, int XF>
+template <int NS>
+struct P2FwdLds {  // As [BM][LDA] bf16 | pre [BM][LDP] fp32 | hsb [BM][LDB] bf16 | hts [32][LDT] bf16
+  static constexpr int BM = 32, LDA = NS * 16 + 8, LDP = 4 * BF_U + 4, LDB = BF_U + 8, LDT = BM + 8;
+  static constexpr int as = 0, pre = as + BM * LDA * 2, hsb = pre + BM * LDP * 4, hts = hsb + BM * LDB * 2;
+  static constexpr int bytes = hts + BF_U * LDT * 2;
+  static_assert(bytes <= SV_LDS_BYTES, "LDS of a CU");
+};
+template <int NS, int XF>
 __global__ __launch_bounds__(256, 1) void lstm_persist2_fwd_bf16_kernel(const bf16_t* __restrict__ whh_bf,
                                                                        bf16_t* __restrict__ gates,
                                                                        float* __restrict__ c_tm,
@@ -224,24 +239,21 @@ __global__ __launch_bounds__(256, 1) void lstm_persist2_fwd_bf16_kernel(const bf
                                                                        bf16_t* __restrict__ hT, long ldhT, int T,
                                                                        int Bp, int B, int H, unsigned* cnt, int nub,
                                                                        int xcd, unsigned* status, unsigned limit,
-                                                                       int fault, int pipe,
+                                                                       int fault,
                                                                        const bf16_t* __restrict__ x_bf,
                                                                        const bf16_t* __restrict__ wih_bf,
                                                                        const float* __restrict__ b_ih,
                                                                        const float* __restrict__ b_hh) {
-  if (!SV_PDBG) pipe = 1;  // (the non-pipelined k-loop: A/B builds only)
-  constexpr int K = NS * 16, LDA = K + 8, HALF = NS / 2 * 16;
-  constexpr int LDP = 4 * BF_U + 4;      // pre [BM][LDP] fp32
-  constexpr int LDB = BF_U + 8;          // hsb [BM][LDB] bf16 (h tile, row-major)
-  constexpr int LDT = BM + 8;            // hts [32][LDT] bf16 (h tile, transposed)
-  constexpr int KR = BM / 32;            // 32-row halves of the tile (rows per thread)
+  using Lds = P2FwdLds<NS>;
+  constexpr int BM = Lds::BM, K = NS * 16, LDA = Lds::LDA, HALF = NS / 2 * 16;
+  constexpr int LDP = Lds::LDP, LDB = Lds::LDB, LDT = Lds::LDT;
+  constexpr int KR = BM / 32;  // (1: the 64-row form is gone)
   static_assert(NS % 2 == 0, "two staging halves");
-  static_assert(BM == 32 || BM == 64, "row tile");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  bf16_t* As = reinterpret_cast<bf16_t*>(smem);                          // [BM][LDA]
-  float* pre = reinterpret_cast<float*>(smem + BM * LDA * 2);            // [BM][LDP]
-  bf16_t* hsb = reinterpret_cast<bf16_t*>(pre + BM * LDP);               // [BM][LDB]
-  bf16_t* hts = hsb + BM * LDB;                                          // [32][LDT]
+  bf16_t* As = reinterpret_cast<bf16_t*>(smem + Lds::as);
+  float* pre = reinterpret_cast<float*>(smem + Lds::pre);
+  bf16_t* hsb = reinterpret_cast<bf16_t*>(smem + Lds::hsb);
+  bf16_t* hts = reinterpret_cast<bf16_t*>(smem + Lds::hts);
   const int tid = threadIdx.x, lane = tid & 63, g = tid >> 6;
   const int r = lane & 31, hh = lane >> 5;
   int ub, rb;
@@ -252,19 +264,7 @@ __global__ __launch_bounds__(256, 1) void lstm_persist2_fwd_bf16_kernel(const bf
   const unsigned producers = nub;
   // this wave's W_hh fragments: B[k][n] = W[g H + j0 + n][k], lane (n = r, k = 16 s + 8 hh .. +7)
   bf16x8_t wreg[NS];
-  {
-    const bool wok = j0 + r < H;
-    const bf16_t* wrow = whh_bf + ((long)g * H + j0 + r) * K + 8 * hh;
-#pragma unroll
-    for (int s2 = 0; s2 < NS; ++s2) {
-      bf16x8_t z = {};
-      wreg[s2] = wok ? *reinterpret_cast<const bf16x8_t*>(wrow + 16 * s2) : z;
-    }
-    // the weights live in AGPRs (MFMA reads B from them directly): the VGPRs stay free for the
-    // x-projection prefetch and the A-fragment ring of the recurrent MFMAs
-#pragma unroll
-    for (int s2 = 0; s2 < NS; ++s2) asm volatile("" : "+a"(wreg[s2]));
-  }
+  wstat_load(whh_bf + ((long)g * H + j0 + r) * K + 8 * hh, j0 + r < H, wreg);
   // fused input projection (XF > 0): W_ih fragments of this wave's 32 gate columns (k = 16 s +
   // 8 hh .. +7, zero past F = 8 XF) and the column's bias b_ih + b_hh
   constexpr int XS = (XF + 1) / 2;  // k-steps of 16
@@ -274,6 +274,7 @@ __global__ __launch_bounds__(256, 1) void lstm_persist2_fwd_bf16_kernel(const bf
   if constexpr (XF > 0) {
     const int col = g * H + j0 + r;
     const bool wok = j0 + r < H;
+    // (this kernel's own text: as a helper shared with the wide forward it moved a vmcnt in the loop)
 #pragma unroll
     for (int s2 = 0; s2 < XS; ++s2) {
       bf16x8_t z = {};
@@ -285,55 +286,39 @@ __global__ __launch_bounds__(256, 1) void lstm_persist2_fwd_bf16_kernel(const bf
       if (b_hh) xbias += b_hh[col];
     }
   }
-  // x_t A fragments (rows b0 + r (+32), k = 16 s + 8 hh), prefetched a step ahead; rows past B
-  // and k past F read zeros
-  u32x4_t xa[XS > 0 ? XS : 1][BM / 32];
+  // x_t A fragments (rows b0 + r, k = 16 s + 8 hh); rows past B and k past F read zeros
+  u32x4_t xa[XS > 0 ? XS : 1];
   auto load_x = [&](int tt) {
     if constexpr (XF > 0) {
       const __amdgpu_buffer_rsrc_t rxs = sv_rsrc(x_bf + (long)tt * B * F, (unsigned)((long)B * F * 2));
 #pragma unroll
-      for (int s2 = 0; s2 < XS; ++s2)
-#pragma unroll
-        for (int m = 0; m < BM / 32; ++m) {
-          const unsigned off = 16 * s2 + 8 * hh < F ? ((unsigned)(b0 + 32 * m + r) * (unsigned)F + 16 * s2 + 8 * hh) * 2u
-                                                    : 0xFFFFFFF0u;
-          xa[s2][m] = __builtin_amdgcn_raw_buffer_load_b128(rxs, off, 0, 0);
-        }
+      for (int s2 = 0; s2 < XS; ++s2) {
+        const unsigned off = 16 * s2 + 8 * hh < F ? ((unsigned)(b0 + r) * (unsigned)F + 16 * s2 + 8 * hh) * 2u : 0xFFFFFFF0u;
+        xa[s2] = __builtin_amdgcn_raw_buffer_load_b128(rxs, off, 0, 0);
+      }
     }
   };
-  // elementwise map: thread -> 4 consecutive units (u4) x rows brow (+ 32)
+  // elementwise map: thread -> 4 consecutive units (u4) of row brow
   const int u4 = (tid & 7) * 4, brow = tid >> 3;
   const long Bv = B;
-  float cst[KR][4];
-#pragma unroll
-  for (int k = 0; k < KR; ++k)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) cst[k][v] = 0.f;
+  float cst[4] = {0.f, 0.f, 0.f, 0.f};
   // staging map of one half (BM rows x HALF bf16 = BM * HALF / 8 16-B chunks over 256 threads)
   constexpr int CH = BM * HALF / 8 / 256;
   // bf16(x W_ih^T + b) of step t (K1 output): 8-B buffer loads of 4 units, rows past B read zeros
-  uint2 xg[KR][4];
+  uint2 xg[4];
   auto load_xg = [&](int tt) {
     if constexpr (XF > 0) {
       load_x(tt);
       return;
     }
     const __amdgpu_buffer_rsrc_t rx = sv_rsrc(gates + (long)tt * BG, (unsigned)(BG * 2));
-#pragma unroll
-    for (int k = 0; k < KR; ++k) {
-      const long gb = b0 + brow + 32 * k;
-      const long gbv = gb < Bv ? gb : Bv + 64;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const u32x2_t x = __builtin_amdgcn_raw_buffer_load_b64(rx, (unsigned)((gbv * G + q * H + j0 + u4) * 2), 0, 0);
-        xg[k][q] = uint2{x.x, x.y};
-      }
-    }
+    const long gb = b0 + brow;
+    persist_load_xg(rx, gb < Bv ? gb : Bv + 64, G, H, j0 + u4, xg);
   };
   for (int t = 0; t < T; ++t) {
-    f32x16 acc0, acc1;
+    f32x16 acc0;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) acc0[i] = acc1[i] = 0.f;
+    for (int i = 0; i < 16; ++i) acc0[i] = 0.f;
     if (t > 0) {
       if (tid == 0) persist_wait(my_cnt, producers * (unsigned)t, status, limit, 1u);
       __syncthreads();
@@ -360,46 +345,30 @@ __global__ __launch_bounds__(256, 1) void lstm_persist2_fwd_bf16_kernel(const bf
       // copied right after the loads, exposing the whole round trip)
       load_xg(t);
       __builtin_amdgcn_sched_barrier(0);
-      if (pipe) {  // A fragments P k-steps ahead of the MFMAs (sv_bf16.h)
-        f32x16 accs[KR];
-        accs[0] = acc0;
-        if constexpr (BM == 64) accs[KR - 1] = acc1;
-        mfma_lds_pipe<NS, KR, (BM == 64 ? 3 : 4)>(As + r * LDA + 8 * hh, 32 * LDA, wreg, accs);
+      {  // A fragments 4 k-steps ahead of the MFMAs (mfma_lds_pipe, sv_bf16.h)
+        f32x16 accs[1] = {acc0};
+        mfma_lds_pipe<NS, 1, 4>(As + r * LDA + 8 * hh, 32 * LDA, wreg, accs);
         acc0 = accs[0];
-        if constexpr (BM == 64) acc1 = accs[KR - 1];
-      } else {
-#pragma unroll
-        for (int s2 = 0; s2 < NS; ++s2) {
-          const bf16x8_t a0 = *reinterpret_cast<const bf16x8_t*>(As + r * LDA + 16 * s2 + 8 * hh);
-          acc0 = mfma_bf16(a0, wreg[s2], acc0);
-          if constexpr (BM == 64) {
-            const bf16x8_t a1 = *reinterpret_cast<const bf16x8_t*>(As + (32 + r) * LDA + 16 * s2 + 8 * hh);
-            acc1 = mfma_bf16(a1, wreg[s2], acc1);
-          }
-        }
       }
     } else {
       load_xg(0);
     }
     if constexpr (XF > 0) {  // pre-activation = recurrent part + (x_t W_ih^T + b_ih + b_hh)
-      f32x16 x0, x1;
+      f32x16 x0;
 #pragma unroll
-      for (int i = 0; i < 16; ++i) x0[i] = x1[i] = 0.f;
+      for (int i = 0; i < 16; ++i) x0[i] = 0.f;
 #pragma unroll
-      for (int s2 = 0; s2 < XS; ++s2) {
-        x0 = mfma_bf16(__builtin_bit_cast(bf16x8_t, xa[s2][0]), wx[s2], x0);
-        if constexpr (BM == 64) x1 = mfma_bf16(__builtin_bit_cast(bf16x8_t, xa[s2][1]), wx[s2], x1);
-      }
+      for (int s2 = 0; s2 < XS; ++s2) x0 = mfma_bf16(__builtin_bit_cast(bf16x8_t, xa[s2]), wx[s2], x0);
       add_round_bf16x(acc0, x0, xbias);
-      if constexpr (BM == 64) add_round_bf16x(acc1, x1, xbias);
     }
     // gate exchange: wave g's [BM rows][32 units] -> pre[row][g * 32 + unit]
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       pre[acc_row(i, lane) * LDP + g * BF_U + r] = acc0[i];
-      if constexpr (BM == 64) pre[(32 + acc_row(i, lane)) * LDP + g * BF_U + r] = acc1[i];
     }
     __syncthreads();
+    // (KR = 1: the [KR] arrays and the two one-pass loops over them stay -- as scalars and plain
+    // blocks they moved waits in this kernel's loop)
     uint2 act[KR][4];
     float4 cv[KR], hv[KR];
 #pragma unroll
@@ -413,7 +382,7 @@ __global__ __launch_bounds__(256, 1) void lstm_persist2_fwd_bf16_kernel(const bf
       float4 xf[4];
       if constexpr (XF == 0) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) xf[q] = unpack_bf4(xg[k][q]);
+        for (int q = 0; q < 4; ++q) xf[q] = unpack_bf4(xg[q]);
       }
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
@@ -424,8 +393,8 @@ __global__ __launch_bounds__(256, 1) void lstm_persist2_fwd_bf16_kernel(const bf
           for (int q = 0; q < 4; ++q) xv[q] = xf[q][v];
         }
         float a4[4], h;
-        const float c = lstm_cell_fwd(pv, xv, cst[k][v], a4, h);
-        cst[k][v] = c;
+        const float c = lstm_cell_fwd(pv, xv, cst[v], a4, h);
+        cst[v] = c;
 #pragma unroll
         for (int q = 0; q < 4; ++q) ao[q][v] = a4[q];
         co[v] = c;
@@ -448,26 +417,15 @@ __global__ __launch_bounds__(256, 1) void lstm_persist2_fwd_bf16_kernel(const bf
     }
     __syncthreads();  // hsb, hts complete
     // the hand-off: h_t bf16, BM rows x 4 chunks of 8 units, 16-B sc1 stores
-    {
-      const int row = tid >> 2, c = tid & 3, gb = b0 + row;
-      const __amdgpu_buffer_rsrc_t rw = sv_rsrc(h_bf + (long)(t + 1) * BH, (unsigned)(BH * 2));
-      if (row < BM && gb < B && j0 + 8 * c < H) {
-        const uint4 v = *reinterpret_cast<const uint4*>(hsb + row * LDB + 8 * c);
-        __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{v.x, v.y, v.z, v.w}, rw,
-                                               ((unsigned)gb * (unsigned)H + (unsigned)(j0 + 8 * c)) * 2u, 0,
-                                               16 /* sc1 */);
-      }
-    }
+    persist_h_store<BM, BF_U, LDB>(hsb, sv_rsrc(h_bf + (long)(t + 1) * BH, (unsigned)(BH * 2)), b0, j0, B, H, tid);
     // publish h_t: the hand-off stores drained, barrier, one lane arrives
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0 && persist_arrive_ok(fault, t == 0))
-      __hip_atomic_fetch_add(my_cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    persist_publish(my_cnt, fault, t == 0);
     // off the critical chain: activations, c, h and hT of step t
 #pragma unroll
     for (int k = 0; k < KR; ++k) {
       const long gb = b0 + brow + 32 * k;
       if (gb < Bv) {
+        // (own text: persist_row_store moved waits in this kernel's loop)
         bf16_t* gp = gates + (long)t * BG + gb * G + j0 + u4;
 #pragma unroll
         for (int q = 0; q < 4; ++q) *reinterpret_cast<uint2*>(gp + q * H) = act[k][q];
@@ -481,9 +439,7 @@ __global__ __launch_bounds__(256, 1) void lstm_persist2_fwd_bf16_kernel(const bf
       constexpr int CPR = BM / 8;
       const int u = tid / CPR, c = tid % CPR, gb = b0 + 8 * c;
       if (u < BF_U && gb < Bp && j0 + u < H) {
-        bf16_t* row = hT + (long)(j0 + u) * ldhT;
-        *reinterpret_cast<uint4*>(row + (long)(t + 1) * Bp + gb) = *reinterpret_cast<const uint4*>(hts + u * LDT + 8 * c);
-        if (t == 0) *reinterpret_cast<uint4*>(row + gb) = uint4{0u, 0u, 0u, 0u};
+        persist_hT_store(hT, ldhT, j0 + u, t, Bp, gb, hts + u * LDT + 8 * c);
       }
     }
   }
@@ -503,35 +459,43 @@ __global__ __launch_bounds__(256, 1) void lstm_persist2_fwd_bf16_kernel(const bf
 // and are summed in gate order 0..3 (the per-step kernel's order, each gate accumulated over k
 // in one accumulator as there), so results are bit-identical to lstm_step_bwd_bf16_kernel.
 // dc * f (the cell-gradient carry) and c_{t-1} stay in registers; the elementwise operands of
-// step t-1 load as 16-B vectors right after step t's arrival.  Only the hand-off stores precede
+// step t-1 are staged into LDS (LDS-DMA) right after step t's arrival.  Only the hand-off stores precede
 // the arrival; dG_t row-major (the dx GEMM's operand, skipped when the dx GEMM reads dgf) and
 // transposed (dgT, the dW GEMMs') are stored after it.
 //   acts [T,B,4H] bf16 activated gates, c_tm [T,B,H]; dhup: [T,B,H] (up_full) or [B,H] at t = T-1.
 // Hand-off: hand-off table row 1 of MI355X_MICROARCH.md, as the forward kernel above.
 // ============================================================================
-template <int NS, int P, int BM, bool agpr_w = true, bool EWD = true>
+// LDS of lstm_persist2_bwd_bf16_kernel: red [4][BM][LDR] fp32 (16-B aligned rows; the bias tail's
+// dsum [BM][4 BF_U] fits in it) | dgs [BM][LDG] bf16 (row-major dG tile) | gts [128][LDT] bf16
+// (transposed dG tile) | the step operands staged by LDS-DMA: ewa [BM][16 x 16 B] activations
+// (gate blocks rotated by row), ewc, ewu [BM][32] fp32 c_{t-1} and dh_up
+template <int BM>
+struct P2BwdLds {
+  static constexpr int LDR = BF_U + 4, LDG = 4 * BF_U + 8, LDT = BM + 8;
+  static constexpr int red = 0, dgs = red + 4 * BM * LDR * 4, gts = dgs + BM * LDG * 2, ewa = gts + 4 * BF_U * LDT * 2;
+  static constexpr int ewc = ewa + BM * 256, ewu = ewc + BM * BF_U * 4, bytes = ewu + BM * BF_U * 4;
+  static_assert(bytes <= SV_LDS_BYTES, "LDS of a CU");
+};
+template <int NS, int P, int BM>
 __global__ __launch_bounds__(256, 1) void lstm_persist2_bwd_bf16_kernel(
     const bf16_t* __restrict__ whhT, const bf16_t* __restrict__ acts, const float* __restrict__ c_tm,
     const float* __restrict__ dhup, int up_full, bf16_t* __restrict__ dg, bf16_t* __restrict__ dgT, long lddgT,
     bf16_t* dgf, int T, int Bp, int B, int H, unsigned* cnt, int nub, int xcd, unsigned* status, unsigned limit,
     int fault, int dbg, float* __restrict__ dbp, unsigned long long* __restrict__ stamps) {
   dbg &= SV_PDBG;
-  constexpr int LDR = BF_U + 4;          // red [4][BM][LDR] fp32 (16-B aligned rows)
-  constexpr int LDG = 4 * BF_U + 8;      // dgs [BM][LDG] bf16 (row-major dG tile)
-  constexpr int LDT = BM + 8;            // gts [128][LDT] bf16 (transposed dG tile)
+  using Lds = P2BwdLds<BM>;
+  constexpr int LDR = Lds::LDR, LDG = Lds::LDG, LDT = Lds::LDT;
   constexpr int FRAG = NS * 64 * 8;      // dgf elements of one (row block, gate, row half)
   constexpr int KR = BM / 32;            // 32-row halves of the tile
   static_assert(P >= 1 && P <= NS, "prefetch depth");
   static_assert(BM == 32 || BM == 64, "row tile");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* red = reinterpret_cast<float*>(smem);
-  bf16_t* dgs = reinterpret_cast<bf16_t*>(smem + 4 * BM * LDR * 4);
-  bf16_t* gts = dgs + BM * LDG;
-  // step operands staged by LDS-DMA (EWD): activations [BM][16 x 16 B] (gate blocks rotated by
-  // row), c_{t-1} and dh_up [BM][32] fp32
-  char* ewa = reinterpret_cast<char*>(gts + 4 * BF_U * LDT);
-  float* ewc = reinterpret_cast<float*>(ewa + BM * 256);
-  float* ewu = ewc + BM * BF_U;
+  float* red = reinterpret_cast<float*>(smem + Lds::red);
+  bf16_t* dgs = reinterpret_cast<bf16_t*>(smem + Lds::dgs);
+  bf16_t* gts = reinterpret_cast<bf16_t*>(smem + Lds::gts);
+  char* ewa = smem + Lds::ewa;
+  float* ewc = reinterpret_cast<float*>(smem + Lds::ewc);
+  float* ewu = reinterpret_cast<float*>(smem + Lds::ewu);
   const int tid = threadIdx.x, lane = tid & 63, g = tid >> 6;
   const int r = lane & 31, hh = lane >> 5;
   int ub, rb;
@@ -544,19 +508,7 @@ __global__ __launch_bounds__(256, 1) void lstm_persist2_bwd_bf16_kernel(
   const unsigned producers = nub;
   // W_hh fragments of gate g: B[k][n] = W_hh[g H + k][j0 + n] = whhT[j0 + n][g H + k]
   bf16x8_t wreg[NS];
-  {
-    const bool wok = j0 + r < H;
-    const bf16_t* wrow = whhT + (long)(j0 + r) * G + (long)g * H + 8 * hh;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      bf16x8_t z = {};
-      wreg[s] = wok ? *reinterpret_cast<const bf16x8_t*>(wrow + 16 * s) : z;
-    }
-    if (agpr_w) {  // weights in AGPRs (MFMA B operand): VGPRs free for the A stream and operands
-#pragma unroll
-      for (int s = 0; s < NS; ++s) asm volatile("" : "+a"(wreg[s]));
-    }
-  }
+  wstat_load(whhT + (long)(j0 + r) * G + (long)g * H + 8 * hh, j0 + r < H, wreg);
   // elementwise map: thread -> 4 consecutive units (u4) x rows brow, brow + 32
   const int u4 = (tid & 7) * 4, brow = tid >> 3;
   uint2 av[KR][4];  // 4 units of each gate, bf16
@@ -570,20 +522,15 @@ __global__ __launch_bounds__(256, 1) void lstm_persist2_bwd_bf16_kernel(
     for (int q = 0; q < 4; ++q)
 #pragma unroll
       for (int v = 0; v < 4; ++v) dbs[k][q][v] = 0.f;
-  // step tt's operands except c_tt (carried): 16-B buffer loads, rows past B read zeros (offsets
-  // beyond the slice's range), as do absent operands (zero-size ranges)
-  auto ld4 = [](__amdgpu_buffer_rsrc_t rs, long off_elems) {
-    const u32x4_t x = __builtin_amdgcn_raw_buffer_load_b128(rs, (unsigned)(off_elems * 4), 0, 0);
-    return float4{__uint_as_float(x.x), __uint_as_float(x.y), __uint_as_float(x.z), __uint_as_float(x.w)};
-  };
   const long Bv = B;
-  // EWD: step tt's operands into LDS by buffer_load ... lds (no destination registers, so the
-  // issuing wave does not wait for them; rows past B and absent operands read zeros).  Wave g's
+  // step tt's operands except c_tt (carried) into LDS by buffer_load ... lds (no destination
+  // registers, so the issuing wave does not wait for them; rows past B -- offsets beyond the
+  // slice's range -- and absent operands -- zero-size ranges -- read zeros).  Wave g's
   // instruction j stages 1 KB at LDS position p = (g * n + j) * 64 + lane (16-B units):
   //   acts: row p / 16, slot s = p % 16 holds gate ((s / 4) - row) & 3, 8-unit chunk s % 4
   //   c_{t-1}, dh_up: row p / 8, 4-unit chunk p % 8
-  auto load_ew_lds = [&](int tt) {
-    const float* up = dhup ? (up_full ? dhup + (long)tt * BH : (tt == T - 1 ? dhup : nullptr)) : nullptr;
+  auto load_ew = [&](int tt) {
+    const float* up = persist_dhup(dhup, up_full, tt, T, BH);
     const __amdgpu_buffer_rsrc_t ra_ = sv_rsrc(acts + (long)tt * BG, (unsigned)(BG * 2));
     const __amdgpu_buffer_rsrc_t rc_ = sv_rsrc(c_tm + (long)(tt > 0 ? tt - 1 : 0) * BH, tt > 0 ? (unsigned)(BH * 4) : 0u);
     const __amdgpu_buffer_rsrc_t ru_ = sv_rsrc(up ? up : c_tm, up ? (unsigned)(BH * 4) : 0u);
@@ -605,34 +552,12 @@ __global__ __launch_bounds__(256, 1) void lstm_persist2_bwd_bf16_kernel(
       __builtin_amdgcn_raw_ptr_buffer_load_lds(ru_, (lds_ptr_t)((char*)ewu + (g * NC + j) * 1024), 16, off, 0, 0, 0);
     }
   };
-  auto load_ew = [&](int tt) {
-    if (EWD) {
-      load_ew_lds(tt);
-      return;
-    }
-    const float* up = dhup ? (up_full ? dhup + (long)tt * BH : (tt == T - 1 ? dhup : nullptr)) : nullptr;
-    const __amdgpu_buffer_rsrc_t ra_ = sv_rsrc(acts + (long)tt * BG, (unsigned)(BG * 2));
-    const __amdgpu_buffer_rsrc_t rc_ = sv_rsrc(c_tm + (long)(tt > 0 ? tt - 1 : 0) * BH, tt > 0 ? (unsigned)(BH * 4) : 0u);
-    const __amdgpu_buffer_rsrc_t ru_ = sv_rsrc(up ? up : c_tm, up ? (unsigned)(BH * 4) : 0u);
-#pragma unroll
-    for (int k = 0; k < KR; ++k) {
-      const long gb = b0 + brow + 32 * k;
-      const long gbv = gb < Bv ? gb : Bv + 64;  // rows past B: offsets past every range
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const u32x2_t x = __builtin_amdgcn_raw_buffer_load_b64(ra_, (unsigned)((gbv * G + q * H + j0 + u4) * 2), 0, 0);
-        av[k][q] = uint2{x.x, x.y};
-      }
-      cpv[k] = ld4(rc_, gbv * H + j0 + u4);
-      upv[k] = ld4(ru_, gbv * H + j0 + u4);
-    }
-  };
   {
     const __amdgpu_buffer_rsrc_t rc_ = sv_rsrc(c_tm + (long)(T - 1) * BH, (unsigned)(BH * 4));
 #pragma unroll
     for (int k = 0; k < KR; ++k) {
       const long gb = b0 + brow + 32 * k;
-      cv[k] = ld4(rc_, (gb < Bv ? gb : Bv + 64) * H + j0 + u4);
+      cv[k] = persist_ld_f4(rc_, (gb < Bv ? gb : Bv + 64) * H + j0 + u4);
 #pragma unroll
       for (int v = 0; v < 4; ++v) dcf[k][v] = 0.f;
     }
@@ -641,13 +566,10 @@ __global__ __launch_bounds__(256, 1) void lstm_persist2_bwd_bf16_kernel(
   // phase stamps (dbg & 32): wait, GEMM + partial exchange, cell epilogue, hand-off + arrival,
   // post-arrival issue
   const bool stamp = dbg & 32;
-  unsigned long long ph[5] = {0, 0, 0, 0, 0}, tlast = stamp ? __builtin_amdgcn_s_memtime() : 0;
+  PhaseStamps<5> ps;
+  if (stamp) ps.start();
   auto mark = [&](int i) {
-    if (stamp) {
-      const unsigned long long now = __builtin_amdgcn_s_memtime();
-      ph[i] += now - tlast;
-      tlast = now;
-    }
+    if (stamp) ps.mark(i);
   };
   for (int t = T - 1; t >= 0; --t) {
     f32x16 acc0, acc1;
@@ -657,7 +579,8 @@ __global__ __launch_bounds__(256, 1) void lstm_persist2_bwd_bf16_kernel(
       if (tid == 0 && !(dbg & 1)) persist_wait(my_cnt, producers * (unsigned)(T - 1 - t), status, limit, 2u);
       __syncthreads();
       mark(0);
-      // A fragments of dG_{t+1}: (row half m, k-step s) is the KB at ((rb 4 + g) 2 + m) FRAG + s 512
+      // A fragments of dG_{t+1}: (row half m, k-step s) is the KB at ((rb 4 + g) 2 + m) FRAG + s 512.
+      // (The k-loop stays this kernel's own text: as a shared helper it put 64 B into scratch.)
       const __amdgpu_buffer_rsrc_t ra = sv_rsrc(dgf + (long)(t + 1) * FS, (unsigned)(FS * 2));
       constexpr unsigned kstep = 1024u;
       const unsigned base0 = ((unsigned)((rb * 4 + g) * KR) * (unsigned)FRAG + (unsigned)lane * 8u) * 2u;
@@ -689,10 +612,10 @@ __global__ __launch_bounds__(256, 1) void lstm_persist2_bwd_bf16_kernel(
       red[(g * BM + acc_row(i, lane)) * LDR + r] = acc0[i];
       if constexpr (BM == 64) red[(g * BM + 32 + acc_row(i, lane)) * LDR + r] = acc1[i];
     }
-    if (EWD) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's operand DMA landed
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's operand DMA landed
     __syncthreads();
     mark(1);
-    if (EWD) {  // step t's operands from the LDS image (every wave's DMA retired before the barrier)
+    {  // step t's operands from the LDS image (every wave's DMA retired before the barrier)
 #pragma unroll
       for (int k = 0; k < KR; ++k) {
         const int b = brow + 32 * k;
@@ -721,7 +644,7 @@ __global__ __launch_bounds__(256, 1) void lstm_persist2_bwd_bf16_kernel(
       const float a2[4] = {f2.x, f2.y, f2.z, f2.w};
       const float a3[4] = {f3.x, f3.y, f3.z, f3.w};
       unsigned pk[4][2];
-      float dh4[4];  // (elementwise, the scalar order)
+      float dh4[4];  // (the gate-order sum in this kernel's own scalar form: persist_gate_sum moved LDS waits)
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
         dh4[v] = rs0[v];
@@ -745,20 +668,8 @@ __global__ __launch_bounds__(256, 1) void lstm_persist2_bwd_bf16_kernel(
     mark(2);
     // the hand-off: dG_t in fragment order, BM/4 KB per workgroup as contiguous KB pieces
     // (gate, row half, k-step), 16-B sc1 stores (dbg & 8, profiling only: no global stores)
-    if (!(dbg & 8)) {
-      const __amdgpu_buffer_rsrc_t rw = sv_rsrc(dgf + (long)t * FS, (unsigned)(FS * 2));
-#pragma unroll
-      for (int i = 0; i < 2 * KR; ++i) {
-        const int p = tid + 256 * i, c = p >> 6, l = p & 63;
-        const int gq = c / (2 * KR), m = (c >> 1) % KR, sl = c & 1;
-        const uint4 v = *reinterpret_cast<const uint4*>(dgs + (32 * m + (l & 31)) * LDG + gq * BF_U + 16 * sl +
-                                                        8 * (l >> 5));
-        const unsigned off =
-            ((unsigned)((rb * 4 + gq) * KR + m) * (unsigned)FRAG + (unsigned)(2 * ub + sl) * 512u + (unsigned)l * 8u) *
-            2u;
-        __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{v.x, v.y, v.z, v.w}, rw, off, 0, 16 /* sc1 */);
-      }
-    }
+    if (!(dbg & 8))
+      persist_dgf_store<KR, BF_U, LDG, FRAG>(dgs, sv_rsrc(dgf + (long)t * FS, (unsigned)(FS * 2)), rb, j0, tid);
     // publish dG_t: every store of the hand-off drained, barrier, one lane arrives.  With no
     // row-major dG: the dx GEMM reads the hand-off): the BM / 16 dG^T stores per thread (buffer
     // stores; a piece past Bp to a dropped offset) go out first, and the drain counts them
@@ -766,8 +677,7 @@ __global__ __launch_bounds__(256, 1) void lstm_persist2_bwd_bf16_kernel(
     // would drain them)
     const bool ovl = !dbg && !dg && dgT && 4L * H * lddgT * 2 < (1L << 32) - 64;
     if (ovl) {
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);  // (the dG^T stores stay younger than the hand-off's)
+      persist_behind_begin();
       const __amdgpu_buffer_rsrc_t rt = sv_rsrc(dgT, (unsigned)(4L * H * lddgT * 2));
 #pragma unroll
       for (int i = 0; i < BM / 16; ++i) {
@@ -778,14 +688,11 @@ __global__ __launch_bounds__(256, 1) void lstm_persist2_bwd_bf16_kernel(
             gb < Bp && gj < H ? (unsigned)((((long)gq * H + gj) * lddgT + (long)t * Bp + gb) * 2) : 0xFFFFFFF0u;
         __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{v.x, v.y, v.z, v.w}, rt, off, 0, 0);
       }
-      asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(BM / 16) : "memory");
-      __builtin_amdgcn_sched_barrier(0);
+      persist_behind_drain<BM / 16>();
     } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
+      persist_drain();
     }
-    if (tid == 0 && persist_arrive_ok(fault, t == T - 1))
-      __hip_atomic_fetch_add(my_cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    persist_arrive(my_cnt, fault, t == T - 1);
     mark(3);
     // dG_t row-major (BM rows x 4 gates x 4 chunks of 8 units) and transposed (128 gate-unit
     // rows x BM/8 chunks of 8 batch columns; padding columns get zeros): 16-B plain stores
@@ -818,25 +725,15 @@ __global__ __launch_bounds__(256, 1) void lstm_persist2_bwd_bf16_kernel(
     mark(4);
   }
   if (stamp && tid == 0 && blockIdx.x < SV_NSTAMP_WG)
-    for (int i = 0; i < 5; ++i) stamps[blockIdx.x * SV_NSTAMP + i] = ph[i];
+    for (int i = 0; i < 5; ++i) stamps[blockIdx.x * SV_NSTAMP + i] = ps.ph[i];
   // bias gradients: this tile's column sums (rows in order 0..BM-1), one partial per row block;
   // sv_persist_db_finalize adds the row blocks in order
   if (dbp) {
     __syncthreads();
-    float* dsum = red;  // [BM][4 * BF_U] fp32 (fits in the red region)
 #pragma unroll
-    for (int k = 0; k < KR; ++k)
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        *reinterpret_cast<float4*>(dsum + (brow + 32 * k) * (4 * BF_U) + q * BF_U + u4) =
-            float4{dbs[k][q][0], dbs[k][q][1], dbs[k][q][2], dbs[k][q][3]};
+    for (int k = 0; k < KR; ++k) persist_db_put<BF_U>(red, brow + 32 * k, u4, dbs[k]);
     __syncthreads();
-    if (tid < 4 * BF_U) {
-      const int q = tid / BF_U, gj = j0 + tid % BF_U;
-      float sum = 0.f;
-      for (int b = 0; b < BM; ++b) sum += dsum[b * (4 * BF_U) + tid];
-      if (gj < H) dbp[(long)rb * G + (long)q * H + gj] = sum;
-    }
+    persist_db_colsum<BM, BF_U>(red, tid, j0, H, rb, dbp);
   }
 }
 
@@ -878,24 +775,6 @@ int sv_persist_db_finalize(const float* dbp, int nrb, int G, float* db_ih, float
 // host side
 // ============================================================================
 namespace {
-constexpr int PFWD_LDS_MAIN = 2 * (BF_BM + 4 * BF_U) * (BBK + 8) * 2;
-constexpr int PFWD_LDS_EPI = (BF_BM * (4 * BF_U + 4) + BF_U * (BF_BM + 1)) * 4;
-constexpr int PFWD_LDS = PFWD_LDS_MAIN > PFWD_LDS_EPI ? PFWD_LDS_MAIN : PFWD_LDS_EPI;
-
-// CU count per device, cached (device attributes do not change while the process runs)
-std::atomic<int> g_cus[64];
-int device_cus(int dev) {
-  if (dev < 0 || dev >= 64) return 0;
-  int n = g_cus[dev].load(std::memory_order_relaxed);
-  if (n > 0) return n;
-  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-  g_cus[dev].store(n, std::memory_order_relaxed);
-  return n;
-}
-int current_cus() {
-  int dev = 0;
-  return hipGetDevice(&dev) == hipSuccess ? device_cus(dev) : 0;
-}
 // XCD-grouped tile order for the W-stationary kernels (persist_tile)
 constexpr int kPersistXcd = 1;
 #ifdef SV_FAULT_INJECTION
@@ -912,9 +791,6 @@ int fwd_fault() { return persist_fault() == 1; }
 // polls before a hand-off wait gives up (each poll = one L2 round trip + s_sleep 2: ~2^21 polls
 // is seconds, far beyond any legitimate wait)
 unsigned persist_limit() { return persist_fault() ? (1u << 12) : (1u << 21); }
-unsigned* sync_cnt(unsigned* sync, int chan) {
-  return sync + SV_SYNC_CNT + (size_t)chan * SV_PCNT_ROWS * SV_PCNT_STRIDE;
-}
 }  // namespace
 
 #ifdef SV_FAULT_INJECTION
@@ -928,77 +804,6 @@ extern "C" int sv_test_set_fault(int mode) {
 unsigned sv_persist_limit() { return persist_limit(); }
 int sv_persist_fault(int bwd) { return bwd ? persist_fault() != 0 : fwd_fault(); }
 
-__global__ void sv_zero_counters_kernel(unsigned* cnt, int nchan, long chan_stride, int words) {
-  for (int i = threadIdx.x; i < nchan * words; i += blockDim.x) cnt[(i / words) * chan_stride + i % words] = 0u;
-}
-
-int sv_zero_counters(unsigned* cnt, int nchan, long chan_stride, int words, hipStream_t stream) {
-  if (!cnt || nchan <= 0 || words <= 0) return SV_EARG;
-  hipLaunchKernelGGL(sv_zero_counters_kernel, dim3(1), dim3(256), 0, stream, cnt, nchan, chan_stride, words);
-  return (int)hipGetLastError();
-}
-
-// head bytes up to 16-B alignment, 16-B body, tail bytes
-__global__ void sv_zero_bytes_kernel(char* p, size_t head, size_t n16, size_t tail) {
-  const size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
-  if (i0 < head) p[i0] = 0;
-  uint4* b = reinterpret_cast<uint4*>(p + head);
-  for (size_t i = i0; i < n16; i += stride) b[i] = make_uint4(0u, 0u, 0u, 0u);
-  if (i0 < tail) p[head + 16 * n16 + i0] = 0;
-}
-
-int sv_zero_bytes(void* p, size_t bytes, hipStream_t stream) {
-  if (!bytes) return SV_OK;
-  if (!p) return SV_EARG;
-  const size_t head = std::min(bytes, (size_t)((16 - ((uintptr_t)p & 15)) & 15));
-  const size_t n16 = (bytes - head) / 16, tail = bytes - head - 16 * n16;
-  const size_t blocks = std::max<size_t>(1, std::min<size_t>(2048, (n16 + 255) / 256));
-  hipLaunchKernelGGL(sv_zero_bytes_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (char*)p, head, n16, tail);
-  return (int)hipGetLastError();
-}
-
-// up to SV_ZB_MAX zeroings in one launch (blockIdx.y = buffer): the per-step state resets of the
-// bf16 stack (and, for the layer wavefront, its counter channels)
-struct ZeroBatch {
-  char* p[SV_ZB_MAX];
-  size_t head[SV_ZB_MAX], n16[SV_ZB_MAX], tail[SV_ZB_MAX];
-};
-__global__ void sv_zero_bytes_multi_kernel(const ZeroBatch zb) {
-  const int b = blockIdx.y;
-  char* p = zb.p[b];
-  const size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
-  if (i0 < zb.head[b]) p[i0] = 0;
-  uint4* q = reinterpret_cast<uint4*>(p + zb.head[b]);
-  for (size_t i = i0; i < zb.n16[b]; i += stride) q[i] = make_uint4(0u, 0u, 0u, 0u);
-  if (i0 < zb.tail[b]) p[zb.head[b] + 16 * zb.n16[b] + i0] = 0;
-}
-int sv_zero_bytes_multi(int n, void* const* ptrs, const size_t* bytes, hipStream_t stream) {
-  if (n <= 0) return SV_OK;
-  if (n > SV_ZB_MAX) return SV_EARG;
-  ZeroBatch zb{};
-  size_t most = 0;
-  for (int i = 0; i < n; ++i) {
-    if (!ptrs[i] && bytes[i]) return SV_EARG;
-    char* p = static_cast<char*>(ptrs[i]);
-    zb.p[i] = p;
-    zb.head[i] = std::min(bytes[i], (size_t)((16 - ((uintptr_t)p & 15)) & 15));
-    zb.n16[i] = (bytes[i] - zb.head[i]) / 16;
-    zb.tail[i] = bytes[i] - zb.head[i] - 16 * zb.n16[i];
-    most = std::max(most, zb.n16[i]);
-  }
-  const size_t blocks = std::max<size_t>(1, std::min<size_t>(2048, (most + 255) / 256));
-  hipLaunchKernelGGL(sv_zero_bytes_multi_kernel, dim3((unsigned)blocks, n), dim3(256), 0, stream, zb);
-  return (int)hipGetLastError();
-}
-
-int sv_stream_cus(hipStream_t stream) {
-  int dev = -1;
-  if (stream && hipStreamGetDevice(stream, &dev) == hipSuccess) return device_cus(dev);
-  return current_cus();
-}
-
-extern "C" size_t sv_sync_size(void) { return (size_t)SV_SYNC_WORDS * sizeof(unsigned); }
-
 // can the persistent forward recurrence run these dims co-resident on a device of `cus` CUs?
 int sv_persist_fwd_fits(int B, int H, int cus) {
   const long grid = (long)((H + BF_U - 1) / BF_U) * ((B + BF_BM - 1) / BF_BM);
@@ -1008,34 +813,21 @@ int sv_persist_bwd_fits(int B, int H, int cus) {
   return (H == 768 || H == 64 || H == 96) && sv_persist_fwd_fits(B, H, cus) && (long)B * 4 * H * 2 < (1L << 31);
 }
 // ... on the current device
-extern "C" int sv_persist_fwd_ok(int B, int H) { return sv_persist_fwd_fits(B, H, current_cus()); }
+extern "C" int sv_persist_fwd_ok(int B, int H) { return sv_persist_fwd_fits(B, H, sv_stream_cus(nullptr)); }
+extern "C" int sv_persist_bwd_ok(int B, int H) { return sv_persist_bwd_fits(B, H, sv_stream_cus(nullptr)); }
 extern "C" int sv_wave_ok(int L, int T, int B, int F, int H) {
-  const int cus = current_cus();
+  const int cus = sv_stream_cus(nullptr);
   return sv_wave_fwd_fits(L, T, B, F, H, cus) && sv_wave_bwd_fits(L, B, H, cus);
 }
 
-namespace {
-// row tile of the W-stationary kernels: 32 rows when twice the 64-row grid still fits on the
-// device (B <= 320 at H = 768: c5's per-GPU batch; measured 13.4 -> 10.1 ms at the c5 rank
-// shape), else 64
-int persist_bm(int B, int H, int cus) {
-  const long grid32 = (long)((H + BF_U - 1) / BF_U) * ((B + 31) / 32);
-  return (grid32 <= cus && (B + 31) / 32 <= SV_PCNT_ROWS) ? 32 : 64;
-}
-}  // namespace
-
-// the 16-row wide forward (sv_persist16_fwd_launch): H = 768, whole 16-row blocks, B > 256 (below, the
-// 32 x 32 tile keeps its bit-identity with the per-step schedule), (B / 16) x (H / 64) co-resident
-int pfwd16_ok(int B, int H, int cus) {
-  return H == 768 && B % 16 == 0 && B > 256 && B / 16 <= SV_PCNT_ROWS && (long)(B / 16) * (H / 64) <= cus;
-}
+// row-block size of the backward's fragment-order hand-off (the dx GEMM's A layout)
+int sv_persist_bm(int B, int H, int cus) { return persist_plan(B, H, cus).bwd.bm; }
 
 // can the persistent forward compute layer 0's input projection in-kernel (F = 40 features)?
 int sv_persist_fwd_fusex_ok(int H, int F) { return H == 768 && F == 40; }
 
 // one layer's recurrence (K2 for all t) after its K1 has filled `gates`; on `stream`.  With x_bf
 // (layer 0, sv_persist_fwd_fusex_ok): no K1 -- the kernel forms x_t W_ih^T + b_ih + b_hh itself.
-int pbwd3_ok(int B, int H, int cus);
 int sv_persist_fwd_bf16(int T, int B, int H, const bf16_t* whh_bf, bf16_t* gates, float* c_tm, float* h_tm,
                         bf16_t* h_bf, bf16_t* hT, hipStream_t stream, unsigned* sync, int chan, const bf16_t* x_bf,
                         int F, const bf16_t* wih_bf, const float* b_ih, const float* b_hh, hipEvent_t pre,
@@ -1044,60 +836,45 @@ int sv_persist_fwd_bf16(int T, int B, int H, const bf16_t* whh_bf, bf16_t* gates
   if (!sv_persist_fwd_fits(B, H, cus)) return SV_ESHAPE;
   if (!sync || chan < 0 || chan >= SV_SYNC_CHANNELS) return SV_EARG;
   if (x_bf && (!wih_bf || !sv_persist_fwd_fusex_ok(H, F))) return SV_EARG;
-  unsigned* cnt = sync_cnt(sync, chan);
+  const PersistTile tile = persist_plan(B, H, cus).fwd;
+  // (the 64-row W-stationary forward is gone: no device below 792 CUs reaches it at H = 768)
+  if (tile.kind == PT_U32x64) return SV_ESHAPE;
+  unsigned* cnt = sv_sync_cnt(sync, chan);
   unsigned* status = sync;
   const int Bp = (B + 7) & ~7;
   const long ldhT = (long)(T + 1) * Bp;
-  const bool wst = H == 768;  // W_hh held in registers (else the LDS-staged persistent kernel)
-  // wide tile (32 rows x 64 units, sv_persist3.hip) where the wide backward runs, with or without
-  // the fused layer-0 projection
-  const bool wide = wst && pbwd3_ok(B, H, cus);
-  // 16-row wide tile (sv_persist3.hip, with or without the fused layer-0 projection) where it keeps
-  // the 32-row tile's workgroup count (B in (256, 320] at H = 768 on 256 CUs: c5's rank shape)
-  const bool p16 = wst && !wide && pfwd16_ok(B, H, cus);
-  const int bm = wide ? 32 : p16 ? 16 : wst ? persist_bm(B, H, cus) : BF_BM;
-  const dim3 grid(wide || p16 ? H / 64 : (H + BF_U - 1) / BF_U, (B + bm - 1) / bm);
+  const dim3 grid(tile.nub, tile.nrb);
   hipError_t e = counters_zeroed ? hipSuccess : (hipError_t)sv_zero_counters(cnt, 1, 0, grid.y * SV_PCNT_STRIDE, stream);
   if (e != hipSuccess) return (int)e;
   const unsigned limit = persist_limit();
   const int fault = fwd_fault();
-  constexpr int dbg = 0, pipe = 1;  // (no diagnostic skips: the kernels' dbg bits are for A/B edits); LDS-pipelined A fragments
+  constexpr int dbg = 0;  // (no diagnostic skips: the kernels' dbg bits are for A/B edits)
   if (pre && (e = hipEventRecord(pre, stream)) != hipSuccess) return (int)e;  // timing probe
-  if (p16) {
+  if (tile.kind == PT_FWD16) {
     const int rc = sv_persist16_fwd_launch((int)grid.y, (int)grid.x, stream, whh_bf, gates, c_tm, h_tm, h_bf, hT, ldhT,
                                            T, Bp, B, H, cnt, kPersistXcd, status, limit, fault, x_bf, F, wih_bf, b_ih,
                                            b_hh);
     if (rc) return rc;
-  } else if (wide) {
+  } else if (tile.kind == PT_WIDE) {
     const int rc = sv_persist3_fwd_launch(dim3(grid.x * grid.y), (int)grid.x, stream, whh_bf, gates, c_tm, h_tm, h_bf,
                                           hT, ldhT, T, Bp, B, H, cnt, kPersistXcd, status, limit, fault, x_bf, F,
                                           wih_bf, b_ih, b_hh, dbg);
     if (rc) return rc;
-  } else if (wst) {
-    constexpr int NS = 48, LDA = NS * 16 + 8;
-    const size_t lds = (size_t)bm * LDA * 2 + (size_t)bm * (4 * BF_U + 4) * 4 + (size_t)bm * (BF_U + 8) * 2 +
-                       (size_t)BF_U * (bm + 8) * 2;
+  } else if (tile.kind == PT_U32x32) {
+    constexpr int NS = 48;
     const dim3 g1(grid.x * grid.y);
     const int nub = (int)grid.x, xcd = kPersistXcd;
-    if (x_bf && bm == 32)
-      hipLaunchKernelGGL((lstm_persist2_fwd_bf16_kernel<NS, 32, 5>), g1, dim3(256), lds, stream, whh_bf, gates, c_tm,
-                         h_tm, h_bf, hT, ldhT, T, Bp, B, H, cnt, nub, xcd, status, limit, fault, pipe, x_bf, wih_bf, b_ih,
-                         b_hh);
-    else if (x_bf)
-      hipLaunchKernelGGL((lstm_persist2_fwd_bf16_kernel<NS, 64, 5>), g1, dim3(256), lds, stream, whh_bf, gates, c_tm,
-                         h_tm, h_bf, hT, ldhT, T, Bp, B, H, cnt, nub, xcd, status, limit, fault, pipe, x_bf, wih_bf, b_ih,
-                         b_hh);
-    else if (bm == 32)
-      hipLaunchKernelGGL((lstm_persist2_fwd_bf16_kernel<NS, 32, 0>), g1, dim3(256), lds, stream, whh_bf, gates, c_tm,
-                         h_tm, h_bf, hT, ldhT, T, Bp, B, H, cnt, nub, xcd, status, limit, fault, pipe, nullptr, nullptr,
-                         nullptr, nullptr);
+    if (x_bf)
+      hipLaunchKernelGGL((lstm_persist2_fwd_bf16_kernel<NS, 5>), g1, dim3(256), P2FwdLds<NS>::bytes, stream, whh_bf,
+                         gates, c_tm, h_tm, h_bf, hT, ldhT, T, Bp, B, H, cnt, nub, xcd, status, limit, fault, x_bf, wih_bf,
+                         b_ih, b_hh);
     else
-      hipLaunchKernelGGL((lstm_persist2_fwd_bf16_kernel<NS, 64, 0>), g1, dim3(256), lds, stream, whh_bf, gates, c_tm,
-                         h_tm, h_bf, hT, ldhT, T, Bp, B, H, cnt, nub, xcd, status, limit, fault, pipe, nullptr, nullptr,
-                         nullptr, nullptr);
+      hipLaunchKernelGGL((lstm_persist2_fwd_bf16_kernel<NS, 0>), g1, dim3(256), P2FwdLds<NS>::bytes, stream, whh_bf,
+                         gates, c_tm, h_tm, h_bf, hT, ldhT, T, Bp, B, H, cnt, nub, xcd, status, limit, fault, nullptr,
+                         nullptr, nullptr, nullptr);
   } else {
-    hipLaunchKernelGGL(lstm_persist_fwd_bf16_kernel<4>, grid, dim3(512), PFWD_LDS, stream, whh_bf, gates, c_tm, h_tm,
-                       h_bf, hT, ldhT, T, Bp, B, H, cnt, status, limit, fault, dbg);
+    hipLaunchKernelGGL(lstm_persist_fwd_bf16_kernel<4>, grid, dim3(512), PFwdLds::bytes, stream, whh_bf, gates, c_tm,
+                       h_tm, h_bf, hT, ldhT, T, Bp, B, H, cnt, status, limit, fault, dbg);
   }
   SV_LAUNCH_CHECK();
   if (post && (e = hipEventRecord(post, stream)) != hipSuccess) return (int)e;
@@ -1106,47 +883,21 @@ int sv_persist_fwd_bf16(int T, int B, int H, const bf16_t* whh_bf, bf16_t* gates
 
 // ---- W-stationary persistent backward recurrence ----
 namespace {
-constexpr size_t pbwd_lds(int bm) {
-  return (size_t)4 * bm * (BF_U + 4) * 4 + (size_t)bm * (4 * BF_U + 8) * 2 + (size_t)4 * BF_U * (bm + 8) * 2 +
-         (size_t)bm * 512;  // + the LDS-DMA operand image (EWD)
-}
 // the backward kernels' diagnostic bits: 0 in the product library (an A/B edit sets e.g. 32 = per-phase
 // cycle stamps into the caller's sync block, read by scripts/persist_ab.py, in a build with
 // FLAGS=-DSV_PDBG=-1: the kernels fold the bits away otherwise)
 constexpr int kPbwdDebug = 0;
-template <int NS, int P>
-void launch_pbwd(dim3 grid, int bm, hipStream_t s, const bf16_t* whhT, const bf16_t* acts, const float* c_tm,
+// lstm_persist2_bwd_bf16_kernel<NS, P, BM> on the tile's grid
+template <int NS, int P, int BM>
+void launch_pbwd(const PersistTile& tile, hipStream_t s, const bf16_t* whhT, const bf16_t* acts, const float* c_tm,
                  const float* dhup, int up_full, bf16_t* dg, bf16_t* dgT, long lddgT, bf16_t* dgf, int T, int Bp, int B,
                  int H, unsigned* cnt, unsigned* sync, float* dbp) {
   unsigned long long* stamps = reinterpret_cast<unsigned long long*>(sync + SV_SYNC_STAMP);
-#define SV_PBWD_LAUNCH(BMV, AG, EW)                                                                               \
-  hipLaunchKernelGGL((lstm_persist2_bwd_bf16_kernel<NS, P, BMV, AG, EW>), dim3(grid.x * grid.y), dim3(256), pbwd_lds(BMV), s, \
-                     whhT, acts, c_tm, dhup, up_full, dg, dgT, lddgT, dgf, T, Bp, B, H, cnt, (int)grid.x, kPersistXcd, \
-                     sync, persist_limit(), persist_fault(), kPbwdDebug, dbp, stamps)
-  // weight fragments in AGPRs, step operands staged by LDS-DMA (EWD)
-  if (bm == 32)
-    SV_PBWD_LAUNCH(32, true, true);
-  else
-    SV_PBWD_LAUNCH(64, true, true);
-#undef SV_PBWD_LAUNCH
+  hipLaunchKernelGGL((lstm_persist2_bwd_bf16_kernel<NS, P, BM>), dim3(tile.nub * tile.nrb), dim3(256),
+                     P2BwdLds<BM>::bytes, s, whhT, acts, c_tm, dhup, up_full, dg, dgT, lddgT, dgf, T, Bp, B, H, cnt,
+                     tile.nub, kPersistXcd, sync, persist_limit(), persist_fault(), kPbwdDebug, dbp, stamps);
 }
 }  // namespace
-
-// row tile the persistent kernels use for this batch on a device of `cus` CUs (the dgf layout's
-// row-block size)
-// wide-tile backward (lstm_persist3_bwd_bf16_kernel): H = 768, (H / 64) x (B / 32) co-resident,
-// and only where the 32-unit tile would need 64-row blocks (B > 320 on 256 CUs: c3); at smaller
-// B the 32 x 32 tile's twice-as-many workgroups win (c5 rank 8.30 vs 9.48 ms, c4 rank 4.36 vs
-// 5.65).
-int pbwd3_ok(int B, int H, int cus) {
-  const int nrb = (B + 31) / 32;
-  return H == 768 && nrb <= SV_PCNT_ROWS && (long)(H / 64) * nrb <= cus && persist_bm(B, H, cus) == 64;
-}
-// row-block size of the backward's fragment-order hand-off (the dx GEMM's A layout)
-int sv_persist_bm(int B, int H, int cus) { return pbwd3_ok(B, H, cus) ? 32 : persist_bm(B, H, cus); }
-
-// can the persistent backward recurrence run these dims (W_hh slice in registers: H in {64, 96, 768})?
-extern "C" int sv_persist_bwd_ok(int B, int H) { return sv_persist_bwd_fits(B, H, current_cus()); }
 
 // fragment-order hand-off scratch of the persistent backward (bytes; T slots of nrb*BM x 4H
 // bf16; the 64-row count bounds the 32-row one)
@@ -1167,12 +918,13 @@ int sv_persist_bwd_bf16(int T, int B, int H, const bf16_t* whhT, const bf16_t* a
   const int cus = sv_stream_cus(stream);
   if (!sv_persist_bwd_fits(B, H, cus)) return SV_ESHAPE;
   if (!dgf || ((uintptr_t)dgf & 15) || !sync || chan < 0 || chan >= SV_SYNC_CHANNELS) return SV_EARG;
-  unsigned* cnt = sync_cnt(sync, chan);
+  const PersistTile tile = persist_plan(B, H, cus).bwd;
+  // (the 64-row tile is kept at H = 64 / 96 only: no device below 792 CUs reaches it at H = 768)
+  if (tile.kind == PT_U32x64 && H == 768) return SV_ESHAPE;
+  unsigned* cnt = sv_sync_cnt(sync, chan);
   const int Bp = (B + 7) & ~7;
   const long lddgT = (long)T * Bp;
-  const bool wide = pbwd3_ok(B, H, cus);
-  const int bm = wide ? 32 : persist_bm(B, H, cus);
-  const dim3 grid(wide ? H / 64 : (H + BF_U - 1) / BF_U, (B + bm - 1) / bm);
+  const dim3 grid(tile.nub, tile.nrb);
   // bias-gradient partials [nrb][4H] after the fragment-order slots (db_ih NULL: not computed)
   float* dbp = db_ih ? reinterpret_cast<float*>(reinterpret_cast<char*>(dgf) +
                                                 (size_t)T * ((B + BF_BM - 1) / BF_BM) * BF_BM * 4 * H * sizeof(bf16_t))
@@ -1181,20 +933,24 @@ int sv_persist_bwd_bf16(int T, int B, int H, const bf16_t* whhT, const bf16_t* a
   if (e != hipSuccess) return (int)e;
   if (pre && (e = hipEventRecord(pre, stream)) != hipSuccess) return (int)e;  // timing probe
   // A-fragment prefetch depth 8 at H = 768 (measured: 4 / 16 no better)
-  if (wide) {
+#define SV_PBWD(NS, P, BM) \
+  launch_pbwd<NS, P, BM>(tile, stream, whhT, acts, c_tm, dhup, up_full, dg, dgT, lddgT, dgf, T, Bp, B, H, cnt, sync, dbp)
+  if (tile.kind == PT_WIDE) {
     const int rc = sv_persist3_bwd_launch(dim3(grid.x * grid.y), (int)grid.x, stream, whhT, acts, c_tm, dhup, up_full,
                                           dg, dgT, lddgT, dgf, T, Bp, B, H, cnt, kPersistXcd, sync, persist_limit(),
                                           persist_fault(), kPbwdDebug, dbp);
     if (rc) return rc;
   } else if (H == 768)
-    launch_pbwd<48, 8>(grid, bm, stream, whhT, acts, c_tm, dhup, up_full, dg, dgT, lddgT, dgf, T, Bp, B, H, cnt, sync,
-                       dbp);
+    SV_PBWD(48, 8, 32);
+  else if (H == 96 && tile.bm == 32)
+    SV_PBWD(6, 4, 32);
   else if (H == 96)
-    launch_pbwd<6, 4>(grid, bm, stream, whhT, acts, c_tm, dhup, up_full, dg, dgT, lddgT, dgf, T, Bp, B, H, cnt, sync,
-                      dbp);
+    SV_PBWD(6, 4, 64);
+  else if (tile.bm == 32)
+    SV_PBWD(4, 4, 32);
   else
-    launch_pbwd<4, 4>(grid, bm, stream, whhT, acts, c_tm, dhup, up_full, dg, dgT, lddgT, dgf, T, Bp, B, H, cnt, sync,
-                      dbp);
+    SV_PBWD(4, 4, 64);
+#undef SV_PBWD
   SV_LAUNCH_CHECK();
   if (post && (e = hipEventRecord(post, stream)) != hipSuccess) return (int)e;
   if (dbp && defer) {  // the caller's next launch sums the partials (dbfin_run)
@@ -1211,13 +967,6 @@ int sv_persist_bwd_bf16(int T, int B, int H, const bf16_t* whhT, const bf16_t* a
     SV_LAUNCH_CHECK();
   }
   return SV_OK;
-}
-
-__global__ void dbfin_kernel(const DbFin f) { dbfin_run(f, blockIdx.x); }
-int sv_dbfin_launch(const DbFin& f, hipStream_t stream) {
-  if (f.n <= 0) return SV_OK;
-  hipLaunchKernelGGL(dbfin_kernel, dim3(dbfin_blocks(f, 256)), dim3(256), 0, stream, f);
-  return (int)hipGetLastError();
 }
 
 // ---- layer-wavefront backward (lstm_wave_bwd_bf16_kernel, sv_persist3.hip) ----
@@ -1267,7 +1016,7 @@ int sv_wave_bwd_bf16(int L, int T, int B, int H, const bf16_t* const* whhT, cons
     p += wave_frag_bytes(T, B, H);
     a.dbp[l] = db_ih ? reinterpret_cast<float*>(p) : nullptr;
     p += wave_dbp_bytes(B, H);
-    a.cnt[l] = sync_cnt(sync, ch0 + l);
+    a.cnt[l] = sv_sync_cnt(sync, ch0 + l);
   }
   if (ch0 < 0 || ch0 + L + (zero_next > 0 ? 1 : 0) > SV_SYNC_CHANNELS ||
       zero_next > SV_PCNT_ROWS * SV_PCNT_STRIDE)
@@ -1313,76 +1062,5 @@ int sv_wave_bwd_bf16(int L, int T, int B, int H, const bf16_t* const* whhT, cons
                        4 * H);
     SV_LAUNCH_CHECK();
   }
-  return SV_OK;
-}
-
-// (status guard) loss := NaN when the sync block's status is set: a training step whose
-// recurrences timed out reports a NaN loss instead of a finite wrong one
-__global__ void status_poison_kernel(const unsigned* __restrict__ status, float* __restrict__ x, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n && __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) x[i] = __builtin_nanf("");
-}
-extern "C" int sv_status_poison(const void* sync, float* x, int n, hipStream_t stream) {
-  if (!sync || !x || n <= 0) return SV_EARG;
-  hipLaunchKernelGGL(status_poison_kernel, dim3((n + 255) / 256), dim3(256), 0, stream,
-                     reinterpret_cast<const unsigned*>(sync), x, n);
-  SV_LAUNCH_CHECK();
-  return SV_OK;
-}
-
-// sv_status_poison + the status word reported to the host without a copy or an event (ABI v9):
-// thread 0 stores ((seq << 32) | status) into a slot of caller-owned pinned host memory mapped into
-// the device's address space (system scope, release), so the host reads the outcome of step `seq`
-// by comparing the slot's high word -- the device->pinned copy and the event it needed idled the
-// GPU ~10 us per step
-__global__ void status_report_kernel(const unsigned* __restrict__ status, float* __restrict__ x, int n,
-                                     unsigned long long* slot, unsigned seq) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const unsigned s = __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (i < n && s) x[i] = __builtin_nanf("");
-  if (i == 0)
-    __hip_atomic_store(slot, ((unsigned long long)seq << 32) | s, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-extern "C" int sv_status_report(const void* sync, float* x, int n, void* host_slot_dev, unsigned seq,
-                                hipStream_t stream) {
-  if (!sync || !host_slot_dev || n < 0 || (n > 0 && !x) || ((uintptr_t)host_slot_dev & 7)) return SV_EARG;
-  hipLaunchKernelGGL(status_report_kernel, dim3(n > 0 ? (n + 255) / 256 : 1), dim3(256), 0, stream,
-                     reinterpret_cast<const unsigned*>(sync), x, n,
-                     reinterpret_cast<unsigned long long*>(host_slot_dev), seq);
-  SV_LAUNCH_CHECK();
-  return SV_OK;
-}
-// the device address of pinned host memory (hipHostGetDevicePointer), for sv_status_report's slot
-extern "C" int sv_host_device_ptr(void* host, void** dev) {
-  if (!host || !dev) return SV_EARG;
-  return (int)hipHostGetDevicePointer(dev, host, 0);
-}
-
-// data-parallel status agreement: flag[0..1] := the status's forward / backward bits as floats
-// (two words of the SUM-reduced gradient buffer: a sum over ranks stays nonzero iff any rank set
-// the bit), then status |= the reduced bits on every rank
-__global__ void status_to_flag_kernel(const unsigned* __restrict__ status, float* __restrict__ flag) {
-  if (threadIdx.x == 0) {
-    const unsigned s = __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    flag[0] = (s & 1u) ? 1.f : 0.f;
-    flag[1] = (s & 2u) ? 1.f : 0.f;
-  }
-}
-__global__ void status_merge_kernel(unsigned* __restrict__ status, const float* __restrict__ flag) {
-  if (threadIdx.x == 0) {
-    const unsigned bits = (flag[0] != 0.f ? 1u : 0u) | (flag[1] != 0.f ? 2u : 0u);
-    if (bits) __hip_atomic_fetch_or(status, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-extern "C" int sv_status_to_flag(const void* sync, float* flag, hipStream_t stream) {
-  if (!sync || !flag) return SV_EARG;
-  hipLaunchKernelGGL(status_to_flag_kernel, dim3(1), dim3(64), 0, stream, reinterpret_cast<const unsigned*>(sync), flag);
-  SV_LAUNCH_CHECK();
-  return SV_OK;
-}
-extern "C" int sv_status_merge(void* sync, const float* flag, hipStream_t stream) {
-  if (!sync || !flag) return SV_EARG;
-  hipLaunchKernelGGL(status_merge_kernel, dim3(1), dim3(64), 0, stream, reinterpret_cast<unsigned*>(sync), flag);
-  SV_LAUNCH_CHECK();
   return SV_OK;
 }

@@ -18,6 +18,18 @@
 // NL: the last NL k-steps of the second W_hh half are read from LDS (staged once, 16 B per lane per
 // fragment, prefetched two k-steps ahead) -- the registers cannot hold all 2 x NS fragments beside
 // the step's working set
+// LDS: red [4][BM][LDR] fp32 (the bias tail's dsum [16][4 U] fits in it) | dgs [BM][LDG] bf16
+// (row-major dG tile) | gts [4 U][LDT] bf16 (transposed dG tile) | the step operands staged by
+// LDS-DMA: ewa [BM][512 B] activations (gate q at ((q + row) & 3) * 128), ewc, ewu [BM][U] fp32
+// c_{t-1} and dh_up | wl: the LDS-resident W_hh fragments
+template <int NL>
+struct P3BwdLds {
+  static constexpr int BM = 32, U = 64, LDR = U + 4, LDG = 4 * U + 8, LDT = BM + 8;
+  static constexpr int red = 0, dgs = red + 4 * BM * LDR * 4, gts = dgs + BM * LDG * 2, ewa = gts + 4 * U * LDT * 2;
+  static constexpr int ewc = ewa + BM * 512, ewu = ewc + BM * U * 4, wl = ewu + BM * U * 4;
+  static constexpr int bytes = wl + wstat_wl_bytes(NL);
+  static_assert(bytes <= SV_LDS_BYTES, "LDS of a CU");
+};
 template <int NS, int P, int NL>
 __global__ __launch_bounds__(256, 1) void lstm_persist3_bwd_bf16_kernel(
     const bf16_t* __restrict__ whhT, const bf16_t* __restrict__ acts, const float* __restrict__ c_tm,
@@ -25,20 +37,19 @@ __global__ __launch_bounds__(256, 1) void lstm_persist3_bwd_bf16_kernel(
     bf16_t* dgf, int T, int Bp, int B, int H, unsigned* cnt, int nub, int xcd, unsigned* status, unsigned limit,
     int fault, int dbg, float* __restrict__ dbp, unsigned long long* __restrict__ stamps) {
   dbg &= SV_PDBG;
-  constexpr int BM = 32, U = 64, KR = 2;  // rows, units, row passes of the epilogue (16 rows each)
-  constexpr int LDR = U + 4;              // red [4][BM][LDR] fp32
-  constexpr int LDG = 4 * U + 8;          // dgs [BM][LDG] bf16 (row-major dG tile)
-  constexpr int LDT = BM + 8;             // gts [4U][LDT] bf16 (transposed dG tile)
-  constexpr int FRAG = NS * 64 * 8;       // dgf elements of one (row block, gate)
+  using Lds = P3BwdLds<NL>;
+  constexpr int BM = Lds::BM, U = Lds::U, KR = 2;  // rows, units, row passes of the epilogue (16 rows each)
+  constexpr int LDR = Lds::LDR, LDG = Lds::LDG, LDT = Lds::LDT;
+  constexpr int FRAG = NS * 64 * 8;  // dgf elements of one (row block, gate)
   static_assert(P >= 1 && P <= NS, "prefetch depth");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* red = reinterpret_cast<float*>(smem);
-  bf16_t* dgs = reinterpret_cast<bf16_t*>(smem + 4 * BM * LDR * 4);
-  bf16_t* gts = dgs + BM * LDG;
-  char* ewa = reinterpret_cast<char*>(gts + 4 * U * LDT);  // [BM][512 B]: gate q at ((q + row) & 3) * 128
-  float* ewc = reinterpret_cast<float*>(ewa + BM * 512);    // [BM][U] c_{t-1}
-  float* ewu = ewc + BM * U;                                // [BM][U] dh_up
-  char* wl = reinterpret_cast<char*>(ewu + BM * U);         // [4 waves][NL][64 lanes][16 B]
+  float* red = reinterpret_cast<float*>(smem + Lds::red);
+  bf16_t* dgs = reinterpret_cast<bf16_t*>(smem + Lds::dgs);
+  bf16_t* gts = reinterpret_cast<bf16_t*>(smem + Lds::gts);
+  char* ewa = smem + Lds::ewa;
+  float* ewc = reinterpret_cast<float*>(smem + Lds::ewc);
+  float* ewu = reinterpret_cast<float*>(smem + Lds::ewu);
+  char* wl = smem + Lds::wl;
   const int tid = threadIdx.x, lane = tid & 63, g = tid >> 6;
   const int r = lane & 31, hh = lane >> 5;
   int ub, rb;
@@ -54,23 +65,9 @@ __global__ __launch_bounds__(256, 1) void lstm_persist3_bwd_bf16_kernel(
   bf16x8_t wa[NS], wb[NR];
   {
     const bf16_t* ra = whhT + (long)(j0 + r) * G + (long)g * H + 8 * hh;
-    const bf16_t* rbp = ra + 32 * G;
-    const bool oka = j0 + r < H, okb = j0 + 32 + r < H;
-    const bf16x8_t z = {};
-#pragma unroll
-    for (int s = 0; s < NS; ++s) wa[s] = oka ? *reinterpret_cast<const bf16x8_t*>(ra + 16 * s) : z;
-#pragma unroll
-    for (int s = 0; s < NR; ++s) wb[s] = okb ? *reinterpret_cast<const bf16x8_t*>(rbp + 16 * s) : z;
-#pragma unroll
-    for (int s = NR; s < NS; ++s)
-      *reinterpret_cast<bf16x8_t*>(wl + ((g * NL + s - NR) * 64 + lane) * 16) =
-          okb ? *reinterpret_cast<const bf16x8_t*>(rbp + 16 * s) : z;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) asm volatile("" : "+a"(wa[s]));
-#pragma unroll
-    for (int s = 0; s < 64 - NS; ++s) asm volatile("" : "+a"(wb[s]));  // the AGPRs left: 64 - NS fragments
+    wstat_load_split<NS, NL>(ra, ra + 32 * G, j0 + r < H, j0 + 32 + r < H, wl, g, lane, wa, wb);
   }
-  auto wl_read = [&](int j) { return *reinterpret_cast<const bf16x8_t*>(wl + ((g * NL + j) * 64 + lane) * 16); };
+  auto wl_read = [&](int j) { return wstat_wl_read<NL>(wl, g, lane, j); };
   // elementwise map: thread -> 4 consecutive units (u4) x rows 2 brow, 2 brow + 1
   const int u4 = (tid & 15) * 4, brow = tid >> 4;
   float4 cv[KR];
@@ -103,7 +100,7 @@ __global__ __launch_bounds__(256, 1) void lstm_persist3_bwd_bf16_kernel(
             sv_rsrc(c_tm + (long)(tt > 0 ? tt - 1 : 0) * BH, tt > 0 ? (unsigned)(BH * 4) : 0u);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rc_, (lds_ptr_t)((char*)ewc + (g * 2 + j) * 1024), 16, off, 0, 0, 0);
       } else {
-        const float* up = dhup ? (up_full ? dhup + (long)tt * BH : (tt == T - 1 ? dhup : nullptr)) : nullptr;
+        const float* up = persist_dhup(dhup, up_full, tt, T, BH);
         const __amdgpu_buffer_rsrc_t ru_ = sv_rsrc(up ? up : c_tm, up ? (unsigned)(BH * 4) : 0u);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(ru_, (lds_ptr_t)((char*)ewu + (g * 2 + j) * 1024), 16, off, 0, 0, 0);
       }
@@ -145,22 +142,17 @@ __global__ __launch_bounds__(256, 1) void lstm_persist3_bwd_bf16_kernel(
 #pragma unroll
     for (int k = 0; k < KR; ++k) {
       const long gb = b0 + 2 * brow + k;
-      const u32x4_t x =
-          __builtin_amdgcn_raw_buffer_load_b128(rc_, (unsigned)(((gb < Bv ? gb : Bv + 64) * H + j0 + u4) * 4), 0, 0);
-      cv[k] = float4{__uint_as_float(x.x), __uint_as_float(x.y), __uint_as_float(x.z), __uint_as_float(x.w)};
+      cv[k] = persist_ld_f4(rc_, (gb < Bv ? gb : Bv + 64) * H + j0 + u4);
 #pragma unroll
       for (int v = 0; v < 4; ++v) dcf[k][v] = 0.f;
     }
   }
   load_ew(T - 1);
-  const bool stamp = dbg & 32;
-  unsigned long long ph[5] = {0, 0, 0, 0, 0}, tlast = stamp ? __builtin_amdgcn_s_memtime() : 0;
+  const bool stamp = dbg & 32;  // phase stamps, as lstm_persist2_bwd_bf16_kernel's
+  PhaseStamps<5> ps;
+  if (stamp) ps.start();
   auto mark = [&](int i) {
-    if (stamp) {
-      const unsigned long long now = __builtin_amdgcn_s_memtime();
-      ph[i] += now - tlast;
-      tlast = now;
-    }
+    if (stamp) ps.mark(i);
   };
   for (int t = T - 1; t >= 0; --t) {
     f32x16 acc0, acc1;
@@ -218,11 +210,7 @@ __global__ __launch_bounds__(256, 1) void lstm_persist3_bwd_bf16_kernel(
           f[q] = unpack_bf4(*reinterpret_cast<const uint2*>(ewa + b * 512 + ((q + b) & 3) * 128 + (u4 >> 3) * 16 +
                                                             (u4 & 7) * 2));
         unsigned pk[4][2];
-        float4 dh4 = r0;  // (elementwise, the scalar order)
-        dh4 += r1;
-        dh4 += r2;
-        dh4 += r3;
-        dh4 += upv;
+        const float4 dh4 = persist_gate_sum(r0, r1, r2, r3, upv);
         float ddv[4][4];
         lstm_cell_bwd_x4(dh4, f[0], f[1], f[2], f[3], cv[k], cpv, dcf[k], ddv);
         pack_dg4(ddv, pk, dbs);
@@ -247,35 +235,20 @@ __global__ __launch_bounds__(256, 1) void lstm_persist3_bwd_bf16_kernel(
     __syncthreads();
     mark(2);
     // the hand-off: 16 KB of dG_t per workgroup in fragment order (gate, k-step), 16-B sc1 stores
-    if (!(dbg & 8)) {
-      const __amdgpu_buffer_rsrc_t rw = sv_rsrc(dgf + (long)t * FS, (unsigned)(FS * 2));
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int p = tid + 256 * i, c = p >> 6, l = p & 63;
-        const int gq = c >> 2, sl = c & 3;
-        const uint4 v = *reinterpret_cast<const uint4*>(dgs + (l & 31) * LDG + gq * U + 16 * sl + 8 * (l >> 5));
-        const unsigned off =
-            ((unsigned)(rb * 4 + gq) * (unsigned)FRAG + (unsigned)(j0 / 16 + sl) * 512u + (unsigned)l * 8u) * 2u;
-        __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{v.x, v.y, v.z, v.w}, rw, off, 0, 16 /* sc1 */);
-      }
-    }
-    // with the dx GEMM on the hand-off (no row-major dG), the step's 4 dG^T stores per
-    // thread go out behind the hand-off stores, before their drain, which counts them (vmcnt(4):
-    // this wave's older hand-off stores done; a raw barrier: __syncthreads' fence would drain them)
+    if (!(dbg & 8))
+      persist_dgf_store<1, U, LDG, FRAG>(dgs, sv_rsrc(dgf + (long)t * FS, (unsigned)(FS * 2)), rb, j0, tid);
+    // with the dx GEMM on the hand-off (no row-major dG), the step's 4 dG^T stores per thread go
+    // out behind the hand-off stores, before their drain, which counts them
     const bool ovl = !dbg && !dg && dgT;
     if (ovl) {
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);  // (the dG^T stores stay younger than the hand-off's)
+      persist_behind_begin();
 #pragma unroll
       for (int i = 8; i < 12; ++i) store_piece(t, i);
-      asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
+      persist_behind_drain<4>();
     } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
+      persist_drain();
     }
-    if (tid == 0 && persist_arrive_ok(fault, t == T - 1))
-      __hip_atomic_fetch_add(my_cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    persist_arrive(my_cnt, fault, t == T - 1);
     mark(3);
     {
       // (dbg, profiling only: 64 skips the operand DMA, 128 the dG / dG^T stores).  The stores
@@ -289,20 +262,12 @@ __global__ __launch_bounds__(256, 1) void lstm_persist3_bwd_bf16_kernel(
     mark(4);
   }
   if (stamp && tid == 0 && blockIdx.x < SV_NSTAMP_WG)
-    for (int i = 0; i < 5; ++i) stamps[blockIdx.x * SV_NSTAMP + i] = ph[i];
-  if (dbp) {
+    for (int i = 0; i < 5; ++i) stamps[blockIdx.x * SV_NSTAMP + i] = ps.ph[i];
+  if (dbp) {  // bias gradients: dsum [16][4U], row pairs (2 brow, 2 brow + 1)
     __syncthreads();
-    float* dsum = red;  // [16][4U] fp32: row pairs (2 brow, 2 brow + 1)
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      *reinterpret_cast<float4*>(dsum + brow * (4 * U) + q * U + u4) = float4{dbs[q][0], dbs[q][1], dbs[q][2], dbs[q][3]};
+    persist_db_put<U>(red, brow, u4, dbs);
     __syncthreads();
-    {
-      const int q = tid / U, gj = j0 + tid % U;
-      float sum = 0.f;
-      for (int b = 0; b < 16; ++b) sum += dsum[b * (4 * U) + tid];
-      if (gj < H) dbp[(long)rb * G + (long)q * H + gj] = sum;
-    }
+    persist_db_colsum<16, U>(red, tid, j0, H, rb, dbp);
   }
 }
 
@@ -311,16 +276,14 @@ int sv_persist3_bwd_launch(dim3 grid, int nub, hipStream_t stream, const bf16_t*
                            bf16_t* dgf, int T, int Bp, int B, int H, unsigned* cnt, int xcd, unsigned* sync,
                            unsigned limit, int fault, int dbg, float* dbp) {
   constexpr int NL = 12;
-  constexpr size_t lds = (size_t)4 * 32 * 68 * 4 + (size_t)32 * 264 * 2 + (size_t)256 * 40 * 2 + (size_t)32 * 512 +
-                         (size_t)2 * 32 * 64 * 4 + (size_t)4 * NL * 1024;
   unsigned long long* stamps = reinterpret_cast<unsigned long long*>(sync + SV_SYNC_STAMP);
   // (the operand DMA and the dG / dG^T stores deferred into the next step's k-loop measured slower
   // -- c3 bwd 1205 vs 1086 us per layer: the fragment waits count the older stores -- and deleted)
   // (operand-prefetch helper workgroups on the 16 free CUs, as the fp32 backward has them, measured
   // no gain here: DESIGN §4)
-  hipLaunchKernelGGL((lstm_persist3_bwd_bf16_kernel<48, 8, NL>), grid, dim3(256), lds, stream, whhT, acts, c_tm,
-                     dhup, up_full, dg, dgT, lddgT, dgf, T, Bp, B, H, cnt, nub, xcd, sync, limit, fault, dbg, dbp,
-                     stamps);
+  hipLaunchKernelGGL((lstm_persist3_bwd_bf16_kernel<48, 8, NL>), grid, dim3(256), P3BwdLds<NL>::bytes, stream, whhT,
+                     acts, c_tm, dhup, up_full, dg, dgT, lddgT, dgf, T, Bp, B, H, cnt, nub, xcd, sync, limit, fault, dbg,
+                     dbp, stamps);
   return (int)hipGetLastError();
 }
 
@@ -338,6 +301,14 @@ int sv_persist3_bwd_launch(dim3 grid, int nub, hipStream_t stream, const bf16_t*
 // the K1 path stores it -- lstm_persist2_fwd_bf16_kernel's fused form.
 // h_{t-1} is staged through registers in two halves (measured against LDS-DMA staging and the
 // second half in flight during the first half's MFMAs: both slower, sv_persist3_fwd_launch)
+// LDS: As [BM][LDA] bf16 | pre [BM][LDP] fp32 | hsb [BM][LDB] bf16 | hts [U][LDT] bf16 | wl
+template <int NS, int NL>
+struct P3FwdLds {
+  static constexpr int BM = 32, U = 64, LDA = NS * 16 + 8, LDP = 4 * U + 4, LDB = U + 8, LDT = BM + 8;
+  static constexpr int as = 0, pre = as + BM * LDA * 2, hsb = pre + BM * LDP * 4, hts = hsb + BM * LDB * 2;
+  static constexpr int wl = hts + U * LDT * 2, bytes = wl + wstat_wl_bytes(NL);
+  static_assert(bytes <= SV_LDS_BYTES, "LDS of a CU");
+};
 template <int NS, int NL, int PA, int XF>
 __global__ __launch_bounds__(256, 1) void lstm_persist3_fwd_bf16_kernel(
     const bf16_t* __restrict__ whh_bf, bf16_t* __restrict__ gates, float* __restrict__ c_tm, float* __restrict__ h_tm,
@@ -347,18 +318,16 @@ __global__ __launch_bounds__(256, 1) void lstm_persist3_fwd_bf16_kernel(
   dbg &= SV_PDBG;
   // dbg (SV_PERSIST_DEBUG, profiling only, results invalid): 1 no hand-off waits, 2 no recurrent
   // MFMAs, 8 no post-arrival stores
-  constexpr int BM = 32, U = 64, KR = 2;
-  constexpr int K = NS * 16, LDA = K + 8;
-  constexpr int LDP = 4 * U + 4;  // pre [BM][LDP] fp32
-  constexpr int LDB = U + 8;      // hsb [BM][LDB] bf16
-  constexpr int LDT = BM + 8;     // hts [U][LDT] bf16
+  using Lds = P3FwdLds<NS, NL>;
+  constexpr int BM = Lds::BM, U = Lds::U, KR = 2;
+  constexpr int K = NS * 16, LDA = Lds::LDA, LDP = Lds::LDP, LDB = Lds::LDB, LDT = Lds::LDT;
   constexpr int NR = NS - NL;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  bf16_t* As = reinterpret_cast<bf16_t*>(smem);                // [BM][LDA]
-  float* pre = reinterpret_cast<float*>(smem + BM * LDA * 2);  // [BM][LDP]
-  bf16_t* hsb = reinterpret_cast<bf16_t*>(pre + BM * LDP);     // [BM][LDB]
-  bf16_t* hts = hsb + BM * LDB;                                // [U][LDT]
-  char* wl = reinterpret_cast<char*>(hts + U * LDT);           // [4 waves][NL][64 lanes][16 B]
+  bf16_t* As = reinterpret_cast<bf16_t*>(smem + Lds::as);
+  float* pre = reinterpret_cast<float*>(smem + Lds::pre);
+  bf16_t* hsb = reinterpret_cast<bf16_t*>(smem + Lds::hsb);
+  bf16_t* hts = reinterpret_cast<bf16_t*>(smem + Lds::hts);
+  char* wl = smem + Lds::wl;
   const int tid = threadIdx.x, lane = tid & 63, g = tid >> 6;
   const int r = lane & 31, hh = lane >> 5;
   int ub, rb;
@@ -371,23 +340,9 @@ __global__ __launch_bounds__(256, 1) void lstm_persist3_fwd_bf16_kernel(
   bf16x8_t wa[NS], wb[NR];
   {
     const bf16_t* ra = whh_bf + ((long)g * H + j0 + r) * K + 8 * hh;
-    const bf16_t* rbp = ra + 32L * K;
-    const bool oka = j0 + r < H, okb = j0 + 32 + r < H;
-    const bf16x8_t z = {};
-#pragma unroll
-    for (int s = 0; s < NS; ++s) wa[s] = oka ? *reinterpret_cast<const bf16x8_t*>(ra + 16 * s) : z;
-#pragma unroll
-    for (int s = 0; s < NR; ++s) wb[s] = okb ? *reinterpret_cast<const bf16x8_t*>(rbp + 16 * s) : z;
-#pragma unroll
-    for (int s = NR; s < NS; ++s)
-      *reinterpret_cast<bf16x8_t*>(wl + ((g * NL + s - NR) * 64 + lane) * 16) =
-          okb ? *reinterpret_cast<const bf16x8_t*>(rbp + 16 * s) : z;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) asm volatile("" : "+a"(wa[s]));
-#pragma unroll
-    for (int s = 0; s < 64 - NS; ++s) asm volatile("" : "+a"(wb[s]));
+    wstat_load_split<NS, NL>(ra, ra + 32L * K, j0 + r < H, j0 + 32 + r < H, wl, g, lane, wa, wb);
   }
-  auto wl_read = [&](int j) { return *reinterpret_cast<const bf16x8_t*>(wl + ((g * NL + j) * 64 + lane) * 16); };
+  auto wl_read = [&](int j) { return wstat_wl_read<NL>(wl, g, lane, j); };
   // fused input projection (XF > 0): W_ih fragments of both 32-column halves of gate g (zero past
   // F) and the columns' biases
   constexpr int XS = (XF + 1) / 2, F = 8 * XF;
@@ -440,12 +395,7 @@ __global__ __launch_bounds__(256, 1) void lstm_persist3_fwd_bf16_kernel(
 #pragma unroll
     for (int k = 0; k < KR; ++k) {
       const long gb = b0 + 2 * brow + k;
-      const long gbv = gb < Bv ? gb : Bv + 64;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const u32x2_t x = __builtin_amdgcn_raw_buffer_load_b64(rx, (unsigned)((gbv * G + q * H + j0 + u4) * 2), 0, 0);
-        xg[k][q] = uint2{x.x, x.y};
-      }
+      persist_load_xg(rx, gb < Bv ? gb : Bv + 64, G, H, j0 + u4, xg[k]);
     }
   };
   for (int t = 0; t < T; ++t) {
@@ -586,43 +536,20 @@ __global__ __launch_bounds__(256, 1) void lstm_persist3_fwd_bf16_kernel(
     }
     __syncthreads();  // hsb, hts complete
     // the hand-off: h_t bf16, 32 rows x 8 chunks of 8 units, one 16-B sc1 store per thread
-    {
-      const int row = tid >> 3, c = tid & 7, gb = b0 + row;
-      const __amdgpu_buffer_rsrc_t rw = sv_rsrc(h_bf + (long)(t + 1) * BH, (unsigned)(BH * 2));
-      if (gb < B && j0 + 8 * c < H) {
-        const uint4 v = *reinterpret_cast<const uint4*>(hsb + row * LDB + 8 * c);
-        __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{v.x, v.y, v.z, v.w}, rw,
-                                               ((unsigned)gb * (unsigned)H + (unsigned)(j0 + 8 * c)) * 2u, 0,
-                                               16 /* sc1 */);
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0 && persist_arrive_ok(fault, t == 0))
-      __hip_atomic_fetch_add(my_cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    persist_h_store<BM, U, LDB>(hsb, sv_rsrc(h_bf + (long)(t + 1) * BH, (unsigned)(BH * 2)), b0, j0, B, H, tid);
+    persist_publish(my_cnt, fault, t == 0);
     // off the critical chain: activations, c, h and hT of step t
     if (dbg & 8) continue;
 #pragma unroll
     for (int k = 0; k < KR; ++k) {
       const long gb = b0 + 2 * brow + k;
-      if (gb < Bv) {
-        bf16_t* gp = gates + (long)t * BG + gb * G + j0 + u4;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) *reinterpret_cast<uint2*>(gp + q * H) = act[k][q];
-        *reinterpret_cast<float4*>(c_tm + (long)t * BH + gb * H + j0 + u4) = cv[k];
-        // fp32 h: only h_{T-1} is read (the projection); the next layer and the backward take
-        // the bf16 copies
-        if (t == T - 1) *reinterpret_cast<float4*>(h_tm + (long)(t + 1) * BH + gb * H + j0 + u4) = hv[k];
-      }
+      if (gb < Bv)
+        persist_row_store(gates + (long)t * BG, c_tm + (long)t * BH, h_tm + (long)(t + 1) * BH, t == T - 1, gb, j0 + u4, H,
+                          act[k], cv[k], hv[k]);
     }
     if (hT) {  // 64 unit rows x 4 chunks of 8 batch columns (padding columns get zeros)
       const int u = tid >> 2, c = tid & 3, gb = b0 + 8 * c;
-      if (gb < Bp && j0 + u < H) {
-        bf16_t* row = hT + (long)(j0 + u) * ldhT;
-        *reinterpret_cast<uint4*>(row + (long)(t + 1) * Bp + gb) =
-            *reinterpret_cast<const uint4*>(hts + u * LDT + 8 * (c ^ ((u >> 4) & 3)));
-        if (t == 0) *reinterpret_cast<uint4*>(row + gb) = uint4{0u, 0u, 0u, 0u};
-      }
+      if (gb < Bp && j0 + u < H) persist_hT_store(hT, ldhT, j0 + u, t, Bp, gb, hts + u * LDT + 8 * (c ^ ((u >> 4) & 3)));
     }
   }
 }
@@ -631,8 +558,6 @@ int sv_persist3_fwd_launch(dim3 grid, int nub, hipStream_t stream, const bf16_t*
                            float* h_tm, bf16_t* h_bf, bf16_t* hT, long ldhT, int T, int Bp, int B, int H, unsigned* cnt,
                            int xcd, unsigned* status, unsigned limit, int fault, const bf16_t* x_bf, int F,
                            const bf16_t* wih_bf, const float* b_ih, const float* b_hh, int dbg) {
-  constexpr size_t base = (size_t)32 * (768 + 8) * 2 + (size_t)32 * (4 * 64 + 4) * 4 + (size_t)32 * 72 * 2 +
-                          (size_t)64 * 40 * 2;
   // h_{t-1} staged through registers in two halves.  Measured alternatives (bit-identical results,
   // deleted): LDS-DMA staging 921 vs 843 us per layer at c3 (r05, on the scalar-addressed W3Dma: 908
   // vs 854); the second half in flight during the first half's MFMAs 4.77 vs 4.67 ms for the
@@ -640,12 +565,12 @@ int sv_persist3_fwd_launch(dim3 grid, int nub, hipStream_t stream, const bf16_t*
   if (x_bf) {  // layer 0, F = 40: the W_ih fragments take registers, so more W_hh fragments live in LDS
     if (F != 40 || !wih_bf) return SV_EARG;
     constexpr int NL = 16;
-    hipLaunchKernelGGL((lstm_persist3_fwd_bf16_kernel<48, NL, 4, 5>), grid, dim3(256), base + (size_t)4 * NL * 1024,
+    hipLaunchKernelGGL((lstm_persist3_fwd_bf16_kernel<48, NL, 4, 5>), grid, dim3(256), (P3FwdLds<48, NL>::bytes),
                        stream, whh_bf, gates, c_tm, h_tm, h_bf, hT, ldhT, T, Bp, B, H, cnt, nub, xcd, status, limit,
                        fault, x_bf, wih_bf, b_ih, b_hh, dbg);
   } else {
     constexpr int NL = 12;
-    hipLaunchKernelGGL((lstm_persist3_fwd_bf16_kernel<48, NL, 4, 0>), grid, dim3(256), base + (size_t)4 * NL * 1024,
+    hipLaunchKernelGGL((lstm_persist3_fwd_bf16_kernel<48, NL, 4, 0>), grid, dim3(256), (P3FwdLds<48, NL>::bytes),
                        stream, whh_bf, gates, c_tm, h_tm, h_bf, hT, ldhT, T, Bp, B, H, cnt, nub, xcd, status, limit,
                        fault, nullptr, nullptr, nullptr, nullptr, dbg);
   }
@@ -669,27 +594,33 @@ int sv_persist3_fwd_launch(dim3 grid, int nub, hipStream_t stream, const bf16_t*
 // XF > 0 (layer 0, F = 8 XF <= 64 features): the input projection formed in the kernel from x_bf [T,B,F] and W_ih
 // [4H,F] (two k-steps of 32, zero past F), rounded to bf16 with its biases as the K1 path stores it, then
 // added to the recurrent part (the 32-row kernels' fused form)
+// LDS: As [BM][LDA] bf16 | pre [BM][LDP] fp32 | hsb [BM][LDB] bf16 | hts [U][LDT] bf16 | wl
+template <int NL>
+struct P16FwdLds {
+  static constexpr int BM = 16, U = 64, K = 768, LDA = K + 8, LDP = 4 * U + 4, LDB = U + 8, LDT = BM + 8;
+  static constexpr int as = 0, pre = as + BM * LDA * 2, hsb = pre + BM * LDP * 4, hts = hsb + BM * LDB * 2;
+  static constexpr int wl = hts + U * LDT * 2, bytes = wl + wstat_wl_bytes(NL);
+  static_assert(bytes <= SV_LDS_BYTES, "LDS of a CU");
+};
 template <int NL, int PA, int XF>
 __global__ __launch_bounds__(256, 1) void lstm_persist16_fwd_bf16_kernel(
     const bf16_t* __restrict__ whh_bf, bf16_t* __restrict__ gates, float* __restrict__ c_tm, float* __restrict__ h_tm,
     bf16_t* h_bf, bf16_t* __restrict__ hT, long ldhT, int T, int Bp, int B, int H, unsigned* cnt, int nub, int xcd,
     unsigned* status, unsigned limit, int fault, const bf16_t* __restrict__ x_bf, const bf16_t* __restrict__ wih_bf,
     const float* __restrict__ b_ih, const float* __restrict__ b_hh) {
-  constexpr int BM = 16, U = 64, K = 768, KS = K / 32;  // 24 k-steps of 32
+  using Lds = P16FwdLds<NL>;
+  constexpr int BM = Lds::BM, U = Lds::U, K = Lds::K, KS = K / 32;  // 24 k-steps of 32
   constexpr int NLS = KS - NL;                          // k-steps whose 4 fragments are all in registers
   constexpr int NRF = 4 * NLS + 3 * NL;                 // register fragments (84 at NL = 12)
   constexpr int NA = 64;                                // ... of which in AGPRs
-  constexpr int LDA = K + 8;                            // As [BM][LDA] bf16
-  constexpr int LDP = 4 * U + 4;                        // pre [BM][LDP] fp32
-  constexpr int LDB = U + 8;                            // hsb [BM][LDB] bf16
-  constexpr int LDT = BM + 8;                           // hts [U][LDT] bf16
+  constexpr int LDA = Lds::LDA, LDP = Lds::LDP, LDB = Lds::LDB, LDT = Lds::LDT;
   static_assert(NRF > NA && PA >= 1 && PA <= KS, "register plan");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  bf16_t* As = reinterpret_cast<bf16_t*>(smem);
-  float* pre = reinterpret_cast<float*>(smem + BM * LDA * 2);
-  bf16_t* hsb = reinterpret_cast<bf16_t*>(pre + BM * LDP);
-  bf16_t* hts = hsb + BM * LDB;
-  char* wl = reinterpret_cast<char*>(hts + U * LDT);  // [4 waves][NL][64 lanes][16 B]
+  bf16_t* As = reinterpret_cast<bf16_t*>(smem + Lds::as);
+  float* pre = reinterpret_cast<float*>(smem + Lds::pre);
+  bf16_t* hsb = reinterpret_cast<bf16_t*>(smem + Lds::hsb);
+  bf16_t* hts = reinterpret_cast<bf16_t*>(smem + Lds::hts);
+  char* wl = smem + Lds::wl;  // [4 waves][NL][64 lanes][16 B]
   const int tid = threadIdx.x, lane = tid & 63, g = tid >> 6;
   const int fr = lane & 15, fq = lane >> 4;
   int ub, rb;
@@ -719,7 +650,7 @@ __global__ __launch_bounds__(256, 1) void lstm_persist16_fwd_bf16_kernel(
 #pragma unroll
     for (int f = 0; f < NA; ++f) asm volatile("" : "+a"(wr[f]));
   }
-  auto wl_read = [&](int j) { return *reinterpret_cast<const bf16x8_t*>(wl + ((g * NL + j) * 64 + lane) * 16); };
+  auto wl_read = [&](int j) { return wstat_wl_read<NL>(wl, g, lane, j); };
   // fused input projection (XF > 0): W_ih fragments of the 4 column tiles (k = 32 s2 + 8 fq, zero
   // past F) and the biases of the lane's accumulator columns (unit 16 nt + 4 fq + v)
   constexpr int F = 8 * XF;
@@ -763,12 +694,8 @@ __global__ __launch_bounds__(256, 1) void lstm_persist16_fwd_bf16_kernel(
       return;
     }
     const __amdgpu_buffer_rsrc_t rx = sv_rsrc(gates + (long)tt * BG, (unsigned)(BG * 2));
-    const long gb = b0 + brow, gbv = gb < B ? gb : (long)B + 64;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const u32x2_t x = __builtin_amdgcn_raw_buffer_load_b64(rx, (unsigned)((gbv * G + q * H + j0 + u4) * 2), 0, 0);
-      xg[q] = uint2{x.x, x.y};
-    }
+    const long gb = b0 + brow;
+    persist_load_xg(rx, gb < B ? gb : (long)B + 64, G, H, j0 + u4, xg);
   };
   constexpr int CH = BM * K / 8 / 256;  // 16-B staging chunks per thread (6)
   for (int t = 0; t < T; ++t) {
@@ -881,7 +808,7 @@ __global__ __launch_bounds__(256, 1) void lstm_persist16_fwd_bf16_kernel(
     }
     __syncthreads();  // hsb, hts complete
     // the hand-off: h_t bf16, 16 rows x 8 chunks of 8 units, one 16-B sc1 store per thread of 128
-    if (tid < BM * 8) {
+    if (tid < BM * 8) {  // (own text: persist_h_store changed this kernel's loop)
       const int row = tid >> 3, c = tid & 7, gb = b0 + row;
       const __amdgpu_buffer_rsrc_t rw = sv_rsrc(h_bf + (long)(t + 1) * BH, (unsigned)(BH * 2));
       if (gb < B && j0 + 8 * c < H) {
@@ -891,28 +818,17 @@ __global__ __launch_bounds__(256, 1) void lstm_persist16_fwd_bf16_kernel(
                                                16 /* sc1 */);
       }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0 && persist_arrive_ok(fault, t == 0))
-      __hip_atomic_fetch_add(my_cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    persist_publish(my_cnt, fault, t == 0);
     // off the critical chain: activations, c, h and h^T of step t
     {
       const long gb = b0 + brow;
-      if (gb < B) {
-        bf16_t* gp = gates + (long)t * BG + gb * G + j0 + u4;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) *reinterpret_cast<uint2*>(gp + q * H) = act[q];
-        *reinterpret_cast<float4*>(c_tm + (long)t * BH + gb * H + j0 + u4) = cv;
-        if (t == T - 1) *reinterpret_cast<float4*>(h_tm + (long)(t + 1) * BH + gb * H + j0 + u4) = hv;
-      }
+      if (gb < B)
+        persist_row_store(gates + (long)t * BG, c_tm + (long)t * BH, h_tm + (long)(t + 1) * BH, t == T - 1, gb, j0 + u4, H,
+                          act, cv, hv);
     }
     if (hT && tid < U * 2) {  // 64 unit rows x 2 chunks of 8 batch columns
       const int u = tid >> 1, c = tid & 1, gb = b0 + 8 * c;
-      if (gb < Bp && j0 + u < H) {
-        bf16_t* row = hT + (long)(j0 + u) * ldhT;
-        *reinterpret_cast<uint4*>(row + (long)(t + 1) * Bp + gb) = *reinterpret_cast<const uint4*>(hts + u * LDT + 8 * c);
-        if (t == 0) *reinterpret_cast<uint4*>(row + gb) = uint4{0u, 0u, 0u, 0u};
-      }
+      if (gb < Bp && j0 + u < H) persist_hT_store(hT, ldhT, j0 + u, t, Bp, gb, hts + u * LDT + 8 * c);
     }
   }
 }
@@ -922,8 +838,7 @@ int sv_persist16_fwd_launch(int nrb, int nub, hipStream_t stream, const bf16_t* 
                             int xcd, unsigned* status, unsigned limit, int fault, const bf16_t* x_bf, int F,
                             const bf16_t* wih_bf, const float* b_ih, const float* b_hh) {
   constexpr int NL = 12;
-  constexpr size_t lds = (size_t)16 * (768 + 8) * 2 + (size_t)16 * (4 * 64 + 4) * 4 + (size_t)16 * 72 * 2 +
-                         (size_t)64 * 24 * 2 + (size_t)4 * NL * 1024;
+  constexpr size_t lds = P16FwdLds<NL>::bytes;
   if (H != 768 || B % 16 || nub != H / 64) return SV_EARG;
   if (x_bf) {  // layer 0, F = 40
     if (F != 40 || !wih_bf) return SV_EARG;
@@ -957,34 +872,36 @@ int sv_persist16_fwd_launch(int nrb, int nub, hipStream_t stream, const bf16_t* 
 // in-kernel dx sums the gates' k-ordered partials in gate order (the dx GEMM sums K = 4H in
 // k-tile order): bf16-level agreement, not bitwise.
 // ============================================================================
+// LDS: red0 / red1 [4][BM][LDR] fp32 (dh_rec and dx partials; the bias tail's dsum [BM][4 U] fits
+// in red0) | dgs [BM][LDG] bf16 | gts [4 U][LDT] bf16 | the step operands staged by LDS-DMA: ewa
+// [BM][256 B] activations (gate q's 64 B at ((q + row) & 3) * 64), ewc [BM][U] fp32 c_{t-1} | wl
+template <int NL>
+struct WaveBwdLds {
+  static constexpr int BM = 32, U = 32, LDR = U + 4, LDG = 4 * U + 8, LDT = BM + 8;
+  static constexpr int red0 = 0, red1 = red0 + 4 * BM * LDR * 4, dgs = red1 + 4 * BM * LDR * 4, gts = dgs + BM * LDG * 2;
+  static constexpr int ewa = gts + 4 * U * LDT * 2, ewc = ewa + BM * 256, wl = ewc + BM * U * 4;
+  static constexpr int bytes = wl + wstat_wl_bytes(NL);
+  static_assert(bytes <= SV_LDS_BYTES, "LDS of a CU");
+};
 template <int NS, int P, int NL>
 __global__ __launch_bounds__(256, 1) void lstm_wave_bwd_bf16_kernel(const WaveBwdArgs a) {
-  constexpr int BM = 32, U = 32;
-  constexpr int LDR = U + 4;         // red0 / red1 [4][BM][LDR] fp32
-  constexpr int LDG = 4 * U + 8;     // dgs [BM][LDG] bf16
-  constexpr int LDT = BM + 8;        // gts [4U][LDT] bf16
+  using Lds = WaveBwdLds<NL>;
+  constexpr int BM = Lds::BM, U = Lds::U, LDR = Lds::LDR, LDG = Lds::LDG, LDT = Lds::LDT;
   constexpr int FRAG = NS * 64 * 8;  // dgf elements of one (row block, gate)
   constexpr int NR = NS - NL;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* red0 = reinterpret_cast<float*>(smem);
-  float* red1 = red0 + 4 * BM * LDR;
-  bf16_t* dgs = reinterpret_cast<bf16_t*>(red1 + 4 * BM * LDR);
-  bf16_t* gts = dgs + BM * LDG;
-  char* ewa = reinterpret_cast<char*>(gts + 4 * U * LDT);  // [BM][256 B]: gate q's 64 B at ((q + row) & 3) * 64
-  float* ewc = reinterpret_cast<float*>(ewa + BM * 256);    // [BM][U] c_{t-1}
-  char* wl = reinterpret_cast<char*>(ewc + BM * U);         // [4 waves][NL][64 lanes][16 B]
+  float* red0 = reinterpret_cast<float*>(smem + Lds::red0);
+  float* red1 = reinterpret_cast<float*>(smem + Lds::red1);
+  bf16_t* dgs = reinterpret_cast<bf16_t*>(smem + Lds::dgs);
+  bf16_t* gts = reinterpret_cast<bf16_t*>(smem + Lds::gts);
+  char* ewa = smem + Lds::ewa;
+  float* ewc = reinterpret_cast<float*>(smem + Lds::ewc);
+  char* wl = smem + Lds::wl;
   const int tid = threadIdx.x, lane = tid & 63, g = tid >> 6;
   const int r = lane & 31, hh = lane >> 5;
   const int T = a.T, B = a.B, H = a.H, nub = a.nub, nrb = a.nrb;
   int ub, rb, l;
-  {
-    const int i = blockIdx.x, n = gridDim.x;
-    const int x = i & 7, q = n >> 3, rr = n & 7;
-    const int Lg = x * q + min(x, rr) + (i >> 3);
-    ub = Lg % nub;
-    rb = (Lg / nub) % nrb;
-    l = Lg / (nub * nrb);
-  }
+  persist_tile_layered(nub, nrb, ub, rb, l);
   const int j0 = ub * U, b0 = rb * BM;
   const long G = 4L * H, BH = (long)B * H, BG = (long)B * G;
   const long FS = (long)nrb * BM * G;
@@ -998,21 +915,9 @@ __global__ __launch_bounds__(256, 1) void lstm_wave_bwd_bf16_kernel(const WaveBw
     const bf16_t* ra = a.whhT[l] + (long)(j0 + r) * G + (long)g * H + 8 * hh;
     const bf16_t* rbp = has_dx ? a.wihT[l] + (long)(j0 + r) * a.ldwih + (long)g * H + 8 * hh : ra;
     const bool ok = j0 + r < H;
-    const bf16x8_t z = {};
-#pragma unroll
-    for (int s = 0; s < NS; ++s) wa[s] = ok ? *reinterpret_cast<const bf16x8_t*>(ra + 16 * s) : z;
-#pragma unroll
-    for (int s = 0; s < NR; ++s) wb[s] = (ok && has_dx) ? *reinterpret_cast<const bf16x8_t*>(rbp + 16 * s) : z;
-#pragma unroll
-    for (int s = NR; s < NS; ++s)
-      *reinterpret_cast<bf16x8_t*>(wl + ((g * NL + s - NR) * 64 + lane) * 16) =
-          (ok && has_dx) ? *reinterpret_cast<const bf16x8_t*>(rbp + 16 * s) : z;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) asm volatile("" : "+a"(wa[s]));
-#pragma unroll
-    for (int s = 0; s < 64 - NS; ++s) asm volatile("" : "+a"(wb[s]));
+    wstat_load_split<NS, NL>(ra, rbp, ok, ok && has_dx, wl, g, lane, wa, wb);
   }
-  auto wl_read = [&](int j) { return *reinterpret_cast<const bf16x8_t*>(wl + ((g * NL + j) * 64 + lane) * 16); };
+  auto wl_read = [&](int j) { return wstat_wl_read<NL>(wl, g, lane, j); };
   // elementwise map: thread -> 4 consecutive units (u4) of row brow
   const int u4 = (tid & 7) * 4, brow = tid >> 3;
   const long gb = b0 + brow, Bv = B;
@@ -1047,18 +952,14 @@ __global__ __launch_bounds__(256, 1) void lstm_wave_bwd_bf16_kernel(const WaveBw
   };
   {
     const __amdgpu_buffer_rsrc_t rc_ = sv_rsrc(a.c[l] + (long)(T - 1) * BH, (unsigned)(BH * 4));
-    const u32x4_t x = __builtin_amdgcn_raw_buffer_load_b128(rc_, (unsigned)((gbv * H + j0 + u4) * 4), 0, 0);
-    cv = float4{__uint_as_float(x.x), __uint_as_float(x.y), __uint_as_float(x.z), __uint_as_float(x.w)};
+    cv = persist_ld_f4(rc_, gbv * H + j0 + u4);
   }
   load_ew(T - 1);
   const int t_end = has_dx ? -1 : 0;
 #ifdef SV_WB_STAMP  // A/B stamp builds only: wave 0's cycles per phase, summed over t = T-2 .. 0
-  unsigned long long ph[6] = {0, 0, 0, 0, 0, 0}, tl = __builtin_amdgcn_s_memtime();
-  auto wmark = [&](int i, int t_) {
-    const unsigned long long n = __builtin_amdgcn_s_memtime();
-    if (t_ < T - 1 && t_ >= 0) ph[i] += n - tl;
-    tl = n;
-  };
+  PhaseStamps<6> ps;
+  ps.start();
+  auto wmark = [&](int i, int t_) { ps.mark(i, t_ < T - 1 && t_ >= 0); };
 #define WB_MARK(i) wmark(i, t)
 #else
 #define WB_MARK(i)
@@ -1156,11 +1057,7 @@ __global__ __launch_bounds__(256, 1) void lstm_wave_bwd_bf16_kernel(const WaveBw
         f[q] = unpack_bf4(*reinterpret_cast<const uint2*>(ewa + b * 256 + ((q + b) & 3) * 64 + (u4 >> 3) * 16 +
                                                           (u4 & 7) * 2));
       unsigned pk[4][2] = {{0u, 0u}, {0u, 0u}, {0u, 0u}, {0u, 0u}};
-      float4 dh4 = r0;  // (elementwise, the scalar order)
-      dh4 += r1;
-      dh4 += r2;
-      dh4 += r3;
-      dh4 += upv;
+      const float4 dh4 = persist_gate_sum(r0, r1, r2, r3, upv);
       float ddv[4][4];
       lstm_cell_bwd_x4(dh4, f[0], f[1], f[2], f[3], cv, cpv, dcf, ddv);
       // (per element here: the packed pairs of pack_dg4 measured +10 us per c4 rank step)
@@ -1183,24 +1080,14 @@ __global__ __launch_bounds__(256, 1) void lstm_wave_bwd_bf16_kernel(const WaveBw
     WB_MARK(2);  // 2: exchange, dh_up, dx_{t+1} hand-off stores, cell backward, dG tiles
     // the dG_t hand-off: 8 KB per workgroup in fragment order (gate, 2 k-steps), 16-B sc1 stores
     if (t >= 0) {
-      const __amdgpu_buffer_rsrc_t rw = sv_rsrc(a.dgf[l] + (long)t * FS, (unsigned)(FS * 2));
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int p = tid + 256 * i, c = p >> 6, ln = p & 63;
-        const int gq = c >> 1, sl = c & 1;
-        const uint4 v = *reinterpret_cast<const uint4*>(dgs + (ln & 31) * LDG + gq * U + 16 * sl + 8 * (ln >> 5));
-        const unsigned off =
-            ((unsigned)(rb * 4 + gq) * (unsigned)FRAG + (unsigned)(2 * ub + sl) * 512u + (unsigned)ln * 8u) * 2u;
-        __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{v.x, v.y, v.z, v.w}, rw, off, 0, 16 /* sc1 */);
-      }
+      persist_dgf_store<1, U, LDG, FRAG>(dgs, sv_rsrc(a.dgf[l] + (long)t * FS, (unsigned)(FS * 2)), rb, j0, tid);
     }
     // the 2 dG_t^T stores per thread (buffer stores; a piece past Bp to a dropped offset)
     // behind the hand-off stores, before their drain, which counts them (vmcnt(2): this wave's
     // older hand-off and dx stores done; a raw barrier: __syncthreads' fence would drain them)
     const bool ovl = t >= 0 && a.dgT[l] && 4L * H * a.lddgT * 2 < (1L << 32) - 64;
     if (ovl) {
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);  // (the dG^T stores stay younger than the hand-off's)
+      persist_behind_begin();
       const __amdgpu_buffer_rsrc_t rt = sv_rsrc(a.dgT[l], (unsigned)(4L * H * a.lddgT * 2));
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
@@ -1211,14 +1098,11 @@ __global__ __launch_bounds__(256, 1) void lstm_wave_bwd_bf16_kernel(const WaveBw
         const unsigned off = gc < a.Bp && gj < H ? (unsigned)(eo * 2) : 0xFFFFFFF0u;
         __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{v.x, v.y, v.z, v.w}, rt, off, 0, 0);
       }
-      asm volatile("s_waitcnt vmcnt(2)\n\ts_barrier" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
+      persist_behind_drain<2>();
     } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
+      persist_drain();
     }
-    if (tid == 0 && persist_arrive_ok(a.fault, t == T - 1))
-      __hip_atomic_fetch_add(my_cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    persist_arrive(my_cnt, a.fault, t == T - 1);
     WB_MARK(3);  // 3: dG_t hand-off stores + drain + arrival
     if (!ovl && t >= 0 && a.dgT[l]) {  // dG_t^T (the dW GEMMs' operand), then the next step's operands
 #pragma unroll
@@ -1239,7 +1123,7 @@ __global__ __launch_bounds__(256, 1) void lstm_wave_bwd_bf16_kernel(const WaveBw
   if (tid == 0 && blockIdx.x < SV_NSTAMP_WG / 2) {  // second half of the stamp slots (the forward's use the first)
     unsigned long long* st =
         reinterpret_cast<unsigned long long*>(a.status + SV_SYNC_STAMP) + (SV_NSTAMP_WG / 2 + blockIdx.x) * SV_NSTAMP;
-    for (int i = 0; i < 5; ++i) st[i] = ph[i];
+    for (int i = 0; i < 5; ++i) st[i] = ps.ph[i];
     st[5] = (unsigned long long)l;
   }
 #endif
@@ -1247,24 +1131,15 @@ __global__ __launch_bounds__(256, 1) void lstm_wave_bwd_bf16_kernel(const WaveBw
   // bias gradients: this tile's column sums over its rows (in order), one partial per row block
   if (a.dbp[l]) {
     __syncthreads();
-    float* dsum = red0;  // [BM][4U] fp32
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      *reinterpret_cast<float4*>(dsum + brow * (4 * U) + q * U + u4) = float4{dbs[q][0], dbs[q][1], dbs[q][2], dbs[q][3]};
+    persist_db_put<U>(red0, brow, u4, dbs);  // dsum [BM][4U]
     __syncthreads();
-    if (tid < 4 * U) {
-      const int q = tid / U, gj = j0 + tid % U;
-      float sum = 0.f;
-      for (int b = 0; b < BM; ++b) sum += dsum[b * (4 * U) + tid];
-      if (gj < H) a.dbp[l][(long)rb * G + (long)q * H + gj] = sum;
-    }
+    persist_db_colsum<BM, U>(red0, tid, j0, H, rb, a.dbp[l]);
   }
 }
 
 int sv_wave_bwd_launch(const WaveBwdArgs& a, hipStream_t stream) {
   constexpr int NL = 12;
-  constexpr size_t lds = (size_t)2 * 4 * 32 * 36 * 4 + (size_t)32 * 136 * 2 + (size_t)128 * 40 * 2 + (size_t)32 * 256 +
-                         (size_t)32 * 32 * 4 + (size_t)4 * NL * 1024;
+  constexpr size_t lds = WaveBwdLds<NL>::bytes;
   hipLaunchKernelGGL((lstm_wave_bwd_bf16_kernel<48, 8, NL>), dim3(WB_L * a.nub * a.nrb), dim3(256), lds, stream, a);
   return (int)hipGetLastError();
 }

@@ -28,8 +28,6 @@
 #include "sv_persist_dev.h"
 #include "../../include/sv_ge2e.h"
 
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-
 namespace {
 constexpr int WV_L = 3;       // layers of one wavefront launch (hp.model.num_layer)
 constexpr int WV_BM = 32;     // rows per workgroup
@@ -61,22 +59,6 @@ struct WaveFwd2Args {
   int stamp;  // SV_WAVE3_STAMP=1 (profiling): per-phase s_memtime cycle sums into the sync block
   int dbg;    // SV_WAVE3_DEBUG (diagnostics)
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wv_rsrc(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
-
-__device__ __forceinline__ void wv_wait(unsigned* c, unsigned target, unsigned* status, unsigned limit) {
-  unsigned spins = 0;
-  while (__hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-    if (__hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
-    __builtin_amdgcn_s_sleep(2);
-    if (++spins > limit) {
-      __hip_atomic_fetch_or(status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return;
-    }
-  }
-}
 
 // acc += A (the tile's LDS image) . W: fragments read 4 ahead (one full scheduling barrier per
 // k-step keeps the reads that far ahead of their MFMAs)
@@ -148,12 +130,12 @@ __device__ __forceinline__ void w3_run(const WaveFwd2Args& a, int l, int ub, int
   const int u4 = (tid & 7) * 4, brow = tid >> 3;
   const long gb = b0 + brow;
   float cst[4] = {0.f, 0.f, 0.f, 0.f};
-  const __amdgpu_buffer_rsrc_t rxs = wv_rsrc(a.x_bf, (unsigned)((long)T * B * WV_F * 2));
+  const __amdgpu_buffer_rsrc_t rxs = sv_rsrc(a.x_bf, (unsigned)((long)T * B * WV_F * 2));
   const unsigned hbytes = (unsigned)((long)(T + 1) * BH * 2);
-  const __amdgpu_buffer_rsrc_t rown = wv_rsrc(a.hb[l], hbytes);
-  const __amdgpu_buffer_rsrc_t rbel = wv_rsrc(L0 ? a.hb[l] : a.hb[l - 1], hbytes);
+  const __amdgpu_buffer_rsrc_t rown = sv_rsrc(a.hb[l], hbytes);
+  const __amdgpu_buffer_rsrc_t rbel = sv_rsrc(L0 ? a.hb[l] : a.hb[l - 1], hbytes);
   if constexpr (!L0) {  // x_0 = h_0^{l-1}
-    if (tid == 0) wv_wait(below, producers, a.status, a.limit);
+    if (tid == 0) persist_wait(below, producers, a.status, a.limit, 1u);
     __syncthreads();
     w3_dma(rbel, 1, B, H, b0, tile_x, g, lane);
   }
@@ -166,18 +148,15 @@ __device__ __forceinline__ void w3_run(const WaveFwd2Args& a, int l, int ub, int
   // STAMP is a template parameter, not a runtime test: a branch between an MFMA and the reads of
   // its accumulators made the compiler's hazard padding too short (the first AGPR read returned a
   // stale a15: rows 27 and 31 of every tile wrong)
-  unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = STAMP ? __builtin_amdgcn_s_memtime() : 0;
+  PhaseStamps<8> ps;
+  if constexpr (STAMP) ps.start();
   auto mark = [&](int i) {
-    if constexpr (STAMP) {
-      const unsigned long long now = __builtin_amdgcn_s_memtime();
-      ph[i] += now - tlast;
-      tlast = now;
-    }
+    if constexpr (STAMP) ps.mark(i);
   };
   for (int t = 0; t < T; ++t) {
     // h_{t-1} (t = 0: slot 0, zeros -- the h-part then adds exact zeros, so every step has the
     // same DMA / wait shape and the compiler can count the waits)
-    if (tid == 0 && t > 0) wv_wait(my_cnt, producers * (unsigned)t, a.status, a.limit);
+    if (tid == 0 && t > 0) persist_wait(my_cnt, producers * (unsigned)t, a.status, a.limit, 1u);
     if (dbg & 1)
       __syncthreads();  // debug: drain everything (the x DMA too) here
     else
@@ -267,9 +246,12 @@ __device__ __forceinline__ void w3_run(const WaveFwd2Args& a, int l, int ub, int
     }
     __syncthreads();
     mark(4);
+    // the hand-off (32 rows x 4 chunks of 8 units, 16-B sc1 stores), then publish h_t.  (Own text:
+    // with persist_h_store the layer-0 loop's DMA descriptors came out scalar, without the waterfall
+    // loops it has today -- another loop than the parent's, so not taken in a refactor.)
     if (tid < WV_BM * 4) {
       const int row = tid >> 2, c = tid & 3, gr = b0 + row;
-      const __amdgpu_buffer_rsrc_t rw = wv_rsrc(a.hb[l] + (long)(t + 1) * BH, (unsigned)(BH * 2));
+      const __amdgpu_buffer_rsrc_t rw = sv_rsrc(a.hb[l] + (long)(t + 1) * BH, (unsigned)(BH * 2));
       if (gr < B && j0 + 8 * c < H) {
         const uint4 v = *reinterpret_cast<const uint4*>(hsb + row * WV_LDB + 8 * c);
         __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{v.x, v.y, v.z, v.w}, rw,
@@ -277,14 +259,14 @@ __device__ __forceinline__ void w3_run(const WaveFwd2Args& a, int l, int ub, int
                                                16 /* sc1 */);
       }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0 && !(a.fault && t == 0 && blockIdx.x == 0))
+    persist_drain();
+    // (the arrival in own text: persist_arrive moved three scalar instructions of the layers 1-2 loop)
+    if (tid == 0 && persist_arrive_ok(a.fault, t == 0))
       __hip_atomic_fetch_add(my_cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     mark(5);
     // off the critical chain: activations, c, h and hT of step t (before the next x DMA, so the
     // counted wait above sees only DMAs behind it)
-    if (gb < B && j0 + u4 < H) {
+    if (gb < B && j0 + u4 < H) {  // (own text: persist_row_store moved a wait in this kernel's loop)
       bf16_t* gp = a.gates[l] + (long)t * BG + gb * G + j0 + u4;
 #pragma unroll
       for (int q = 0; q < 4; ++q) *reinterpret_cast<uint2*>(gp + q * H) = act[q];
@@ -293,14 +275,10 @@ __device__ __forceinline__ void w3_run(const WaveFwd2Args& a, int l, int ub, int
     }
     if (a.hT[l] && tid < BF_U * (WV_BM / 8)) {
       const int u = tid >> 2, c = tid & 3, gc = b0 + 8 * c;
-      if (gc < a.Bp && j0 + u < H) {
-        bf16_t* row = a.hT[l] + (long)(j0 + u) * a.ldhT;
-        *reinterpret_cast<uint4*>(row + (long)(t + 1) * a.Bp + gc) = *reinterpret_cast<const uint4*>(hts + u * WV_LDT + 8 * c);
-        if (t == 0) *reinterpret_cast<uint4*>(row + gc) = uint4{0u, 0u, 0u, 0u};
-      }
+      if (gc < a.Bp && j0 + u < H) persist_hT_store(a.hT[l], a.ldhT, j0 + u, t, a.Bp, gc, hts + u * WV_LDT + 8 * c);
     }
     if (!L0 && t + 1 < T && !xe) {  // x_{t+1}: tile_x is free (every wave is past this step's x-part)
-      if (tid == 0) wv_wait(below, producers * (unsigned)(t + 2), a.status, a.limit);
+      if (tid == 0) persist_wait(below, producers * (unsigned)(t + 2), a.status, a.limit, 1u);
       raw_barrier();
       w3_dma(rbel, t + 2, B, H, b0, tile_x, g, lane);
     }
@@ -308,7 +286,7 @@ __device__ __forceinline__ void w3_run(const WaveFwd2Args& a, int l, int ub, int
   }
   if (STAMP && tid == 0 && blockIdx.x < SV_NSTAMP_WG) {
     unsigned long long* st = reinterpret_cast<unsigned long long*>(a.status + SV_SYNC_STAMP) + blockIdx.x * SV_NSTAMP;
-    for (int i = 0; i < 7; ++i) st[i] = ph[i];
+    for (int i = 0; i < 7; ++i) st[i] = ps.ph[i];
     st[7] = (unsigned long long)l;
   }
 }
@@ -320,16 +298,10 @@ __global__ __launch_bounds__(256, 1) void lstm_wave3_fwd_bf16_kernel(const WaveF
   __shared__ __attribute__((aligned(16))) float pre[WV_BM * WV_LDP];
   __shared__ __attribute__((aligned(16))) bf16_t hsb[WV_BM * WV_LDB];
   __shared__ __attribute__((aligned(16))) bf16_t hts[BF_U * WV_LDT];
-  const int nub = a.nub;
+  static_assert(2 * W3_TILE + WV_BM * WV_LDP * 4 + WV_BM * WV_LDB * 2 + BF_U * WV_LDT * 2 + 16 <= SV_LDS_BYTES,
+                "LDS of a CU (static arrays: the launcher passes no dynamic bytes)");
   int ub, rb, l;
-  {
-    const int i = blockIdx.x, n = gridDim.x;
-    const int x = i & 7, q = n >> 3, rr = n & 7;
-    const int L = x * q + min(x, rr) + (i >> 3);
-    ub = L % nub;
-    rb = (L / nub) % a.nrb;
-    l = L / (nub * a.nrb);
-  }
+  persist_tile_layered(a.nub, a.nrb, ub, rb, l);
   if (l == 0)
     w3_run<true, STAMP>(a, l, ub, rb, tile_x, tile_h, pre, hsb, hts);
   else
@@ -368,7 +340,7 @@ int sv_wave_fwd_bf16(int L, int T, int B, int F, int H, const bf16_t* x_bf, cons
     a.h[l] = h_tm[l];
     a.hb[l] = h_bf[l];
     a.hT[l] = hT[l];
-    a.cnt[l] = sync + SV_SYNC_CNT + (size_t)l * SV_PCNT_ROWS * SV_PCNT_STRIDE;
+    a.cnt[l] = sv_sync_cnt(sync, l);
   }
   // counters_zeroed: the caller zeroed channels 0..L-1 in its state-reset launch
   if (!counters_zeroed)

@@ -326,22 +326,23 @@ def test_stack_bf16(B, F, H, L, T, schedule, need_dx):
 
 @pytest.mark.parametrize("B,T,schedule", bf16_cases.H768_CASES)
 def test_stack_bf16_h768(B, T, schedule):
-    """F = 40, H = 768, L = 3, one B per kernel family (dispatch read in sv_persist.hip:
-    sv_persist_fwd_bf16, persist_bm, pfwd16_ok, pbwd3_ok, sv_persist_bm; sv_wave.hip: sv_wave_fwd_fits;
-    on 256 CUs):
+    """F = 40, H = 768, L = 3, one B per kernel family (dispatch read in sv_persist_plan.h:
+    persist_plan, used by sv_persist_fwd_bf16, sv_persist_bwd_bf16 and sv_persist_bm; sv_wave.hip:
+    sv_wave_fwd_fits; on 256 CUs):
       auto, B = 33, 80        the layer wavefront forward and backward (sv_wave_ok: 3 x 24 x
                               ceil(B / 32) <= 256 workgroups, i.e. B <= 96); B = 33 is a second 32-row
                               block of one row.  Every layer's x-projection is fused (tie-near rule).
       per_layer, B = 84, 160  lstm_persist2_fwd_bf16_kernel / lstm_persist2_bwd_bf16_kernel with the
-                              32-row tile (persist_bm: 24 x ceil(B / 32) <= 256, every B <= 320; B =
+                              32-row tile (persist_plan: 24 x ceil(B / 32) <= 256, every B <= 320; B =
                               84 has a ragged last block and Bp = 88, 160 is five full blocks)
-      per_layer, B = 288      the 16-row wide forward (pfwd16_ok: B % 16 == 0, 256 < B <= 320), the
+      per_layer, B = 288      the 16-row wide forward (fwd16: B % 16 == 0, 256 < B <= 320), the
                               32-row backward
-      per_layer, B = 340      the wide sv_persist3.hip pair (pbwd3_ok: 320 < B <= 672; 340 = 10 x 32
+      per_layer, B = 340      the wide sv_persist3.hip pair (wide: 320 < B <= 672; 340 = 10 x 32
                               + 20, not a multiple of its 32-row tile, Bp = 344)
     The 64-row tile of the W-stationary kernels is not reachable at H = 768 on a 256-CU device:
-    persist_bm returns 64 only for B > 320, where pbwd3_ok takes the wide pair up to B = 672, and
-    beyond B = 640 the 64-row grid (24 x 11) no longer fits; it runs at H = 64 / 96 in
+    the 32-unit tile needs 64 rows only for B > 320, where the wide pair takes over up to B = 672, and
+    beyond B = 640 the 64-row grid (24 x 11) no longer fits; its H = 768 instantiations are gone, and
+    it runs at H = 64 / 96 in
     test_stack_bf16.  Under per_layer layer 0's projection is fused into its recurrence
     (sv_persist_fwd_fusex_ok), layers 1 and 2 take the K1 GEMM, repeated here.  The fp64 reference
     is stock torch fp64 on the device.  Only slot T of the fp32 h_tm is guaranteed."""

@@ -49,7 +49,8 @@ def test_persistent_fwd_bf16_16row_tile_against_per_step(N, M, T):
                                         ((40, 768, 3, 256), 56, 10, 9),    # B = 560: wide tiles, row-major dG
                                         ((40, 768, 2, 256), 16, 10, 7),    # B = 160: 32-row tiles
                                         ((40, 96, 2, 32), 7, 5, 9),        # ragged rows (B = 35)
-                                        ((40, 64, 3, 32), 4, 5, 7)])       # H = 64: 2 unit blocks
+                                        ((40, 64, 3, 32), 4, 5, 7),        # H = 64: 2 unit blocks
+                                        ((40, 64, 2, 32), 205, 10, 3)])    # B = 2050: 33 blocks of 64 rows
 def test_persistent_bwd_bf16_equals_per_step(dims, N, M, T):
     """W-stationary persistent backward recurrence (one launch per layer, dG handed off through
     HBM) vs per-step launches: the same per-gate MFMA order and the same gate-order sum, so dG,
