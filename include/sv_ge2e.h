@@ -565,6 +565,33 @@ int sv_dvector_embed_bf16_frames(int B, int T, int F, int H, int L, const float*
  * pointers or S, P, n_parts < 1 are SV_EARG.  No atomics, no workspace. */
 int sv_dvec_align(const float* emb, int S, int P, const int* part_off, int n_parts, double* out, hipStream_t stream);
 
+/* ---- training batches from a device-resident corpus (added under v12; additive): the LSTM stack's
+ * layer-0 operands cut straight out of the stored utterances, in one launch.  The batch
+ *   x[b][t][f] = corpus[utt[b]][f][start[b] + t],  b < B, t < T, f < F
+ * is never materialised.
+ *   corpus  [n_utt][F][Tc] fp32: utterance-major, then mel, frames contiguous -- the layout of the
+ *           preprocessed speakerK.npy files (data_preprocess.py:46-54), all speakers concatenated
+ *   utt     device int32 [B]: the utterance of row b, clamped into [0, n_utt - 1]
+ *   start   device int32 [B]: its first frame, clamped into [0, Tc - T]; a bad table never forms an
+ *           address outside corpus, and every offset is 64-bit (n_utt F Tc may pass 2^31)
+ *   x_tm    [T][B][F] (fp32), x_bf likewise in bf16
+ *   xT      [F][T Bp]: column t Bp + b holds x[b][t][:], the padding columns b in [B, Bp) are written
+ *           as zeros (the buffer needs no zeroing); may be NULL (a forward that saves no state)
+ * These are the operands sv_frames_to_time_major + sv_transpose (fp32) and sv_frames_to_bf16 (bf16)
+ * make of the materialised batch, bit for bit: the fp32 outputs are copies, the bf16 ones the same
+ * round-to-nearest-even cast.  One launch on `stream`, whose grid depends on (B, T, F, Bp) only; no
+ * workspace, no atomics, no host synchronisation, graph-capturable.  It belongs on the stream of the
+ * step it feeds, ahead of the forward: never on a side stream beside a persistent recurrence, whose
+ * grid must have the CUs to itself (the sync block's status word reports exactly that failure).
+ * SV_EARG: a null corpus, utt, start or x_tm / x_bf; n_utt, B, T or F < 1; xT given with Bp < B.
+ * SV_ESHAPE: T > Tc; F > 128 (the front end's nmels limit); F % 4 or Bp % 4 (fp32), F % 8 or Bp % 8
+ * (bf16; Bp is checked whether or not xT is given); more than 2^20 - 16 rows.  SV_EALIGN: corpus or
+ * an output off a 16-byte boundary, a table off a 4-byte one.  All checks return before any launch. */
+int sv_corpus_batch(const float* corpus, long n_utt, int F, int Tc, const int* utt, const int* start, int B, int T,
+                    float* x_tm, float* xT, int Bp, hipStream_t stream);
+int sv_corpus_batch_bf16(const float* corpus, long n_utt, int F, int Tc, const int* utt, const int* start, int B,
+                         int T, sv_bf16* x_bf, sv_bf16* xT, int Bp, hipStream_t stream);
+
 /* ---- clip_grad_norm_ + SGD step over one flat parameter group (train_speech_embedder.py:63-65)
  * p -= lr * min(1, max_norm / (|g|_2 + 1e-6)) * g; write_grad=1 also scales g in place.
  * sync (may be NULL): a persistent-recurrence sync block; if its status is set the step is

@@ -157,6 +157,8 @@ SIGNATURES = {
     "sv_logmel_ranges": (_c_int, [_P] * 4 + [_c_int] * 6 + [_P, _c_long, _P, _P, _P, _P]),
     "sv_dvector_embed_bf16_frames": (_c_int, [_c_int] * 5 + [_P, _c_int, _P] + [_P] * 6 + [_c_int, _P, _P, _P]),
     "sv_dvec_align": (_c_int, [_P, _c_int, _c_int, _P, _c_int, _P, _P]),
+    "sv_corpus_batch": (_c_int, [_P, _c_long, _c_int, _c_int, _P, _P, _c_int, _c_int, _P, _P, _c_int, _P]),
+    "sv_corpus_batch_bf16": (_c_int, [_P, _c_long, _c_int, _c_int, _P, _P, _c_int, _c_int, _P, _P, _c_int, _P]),
     "sv_clip_sgd_workspace": (_c_size_t, []),
     "sv_clip_sgd_step": (_c_int, [_P, _P, _c_long, _c_float, _c_float, _c_int, _P, _P, _P, _P]),
     "sv_clip_sgd_step2": (_c_int, [_P, _P, _c_long, _c_float, _P, _P, _c_long, _c_float, _c_float, _c_int, _P, _P, _P,

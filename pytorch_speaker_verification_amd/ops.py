@@ -20,6 +20,7 @@ import torch
 
 from ._lib import (SV_DTYPE_BF16, SV_DTYPE_F32, SV_SCHED_CNT_READY, SV_SCHED_NO_EVENTS, SV_SCHED_WT_READY,
                    PersistStatus, call, call_as, lib, loss_id, ptr, require_device, schedule_flags, stream_of)
+from .data_load import CorpusBatch
 
 # timesteps per chunk of the layer-pipelined schedules (measured at c2: 16 / 24 / 32 / 48 / 64 ->
 # 69.3 / 69.7 / 69.1 / 69.5 / 69.6 ms per step)
@@ -230,8 +231,29 @@ def _dx_batch_first(dx, s):
     return dxb
 
 
+def _corpus_batch(x):
+    """x if it is a data_load.CorpusBatch (a batch still in the resident corpus), None for a tensor."""
+    return x if isinstance(x, CorpusBatch) else None
+
+
+def _corpus_prep(entry, cb, x_out, xT, Bp, s):
+    """sv_corpus_batch / sv_corpus_batch_bf16: layer 0's operands x_out [T,B,F] and xT [F, T*Bp] (or
+    None) of the batch cb, cut out of its corpus in one launch on the step's stream s."""
+    data = cb.corpus.data
+    require_device(data)
+    _check_i32_table(cb.utt, "utt")
+    _check_i32_table(cb.start, "start")
+    if cb.utt.shape != cb.start.shape or cb.utt.device != data.device or cb.start.device != data.device:
+        raise RuntimeError("CorpusBatch: utt and start must be [B] tables on the corpus' device")
+    B, T, F = cb.shape
+    call(entry, ptr(data), data.shape[0], F, data.shape[2], ptr(cb.utt), ptr(cb.start), B, T, ptr(x_out), ptr(xT), Bp,
+         s)
+
+
 def embedder_forward(x, layers, w_p, b_p, save=True, products="mfma_f32", status=None, probe=None, schedule="auto"):
-    """x [B,T,F] float32 (batch_first); layers = [(w_ih, w_hh, b_ih, b_hh)] * L.
+    """x [B,T,F] float32 (batch_first), or a data_load.CorpusBatch of that shape (its operands are
+    then cut out of the resident corpus by sv_corpus_batch, bit-identical to those of
+    x = batch.frames()); layers = [(w_ih, w_hh, b_ih, b_hh)] * L.
     Returns (emb [B,P], state).  products: fp32 product mode of the stack (F32_PRODUCT_MODES).
     schedule: 'auto' (the persistent recurrences where they fill the device, sv_lstm_f32_persist_ok),
     'per_step' (layer-pipelined K2 steps) or 'persist'; status: the caller's PersistStatus (sync
@@ -239,7 +261,8 @@ def embedder_forward(x, layers, w_p, b_p, save=True, products="mfma_f32", status
     check_persistent_status()); probe: 2*L events around the layers' persistent launches."""
     prod = _products(products)
     sched = schedule_flags(schedule)
-    require_device(x, w_p, b_p, *[t for l in layers for t in l])
+    cb = _corpus_batch(x)
+    require_device(None if cb else x, w_p, b_p, *[t for l in layers for t in l])
     B, T, F = x.shape
     H = layers[0][1].shape[1]
     L = len(layers)
@@ -250,9 +273,13 @@ def embedder_forward(x, layers, w_p, b_p, save=True, products="mfma_f32", status
     st = EmbedderState()
     st.T, st.B, st.H, st.P = T, B, H, w_p.shape[0]
     x_tm = _f32((T, B, F), dev)
-    call("sv_frames_to_time_major", ptr(x), ptr(x_tm), B, T, F, s)
     Bp = (B + 3) // 4 * 4
-    if save:  # layer-0 input transposed, [F, T*Bp] (column block t = x_t^T, padding columns zero)
+    if cb:  # x_tm and x^T from the corpus in one launch (the padding columns are the kernel's)
+        st.xT0 = _f32((F, T * Bp), dev) if save else None
+        _corpus_prep("sv_corpus_batch", cb, x_tm, st.xT0, Bp, s)
+    else:
+        call("sv_frames_to_time_major", ptr(x), ptr(x_tm), B, T, F, s)
+    if save and not cb:  # layer-0 input transposed, [F, T*Bp] (column block t = x_t^T, padding columns zero)
         if Bp == B:
             st.xT0 = _f32((F, T * B), dev)
             call("sv_transpose", ptr(x_tm), F, T * B, F, ptr(st.xT0), T * B, s)
@@ -352,9 +379,12 @@ def embedder_forward_bf16(x, layers, w_p, b_p, save=True, status=None, probe=Non
     status: the caller's PersistStatus (sync block of the persistent recurrences); None = a
     fresh one, checked at the next call / check_persistent_status().  probe: 2*L timing events
     around the layers' persistent recurrences (include/sv_ge2e.h).  schedule: 'auto' (default),
-    'per_layer', 'per_step' or 'persist' (the SV_SCHED_* flags of include/sv_ge2e.h)."""
+    'per_layer', 'per_step' or 'persist' (the SV_SCHED_* flags of include/sv_ge2e.h).
+    x may be a data_load.CorpusBatch: sv_corpus_batch_bf16 then writes x_bf and x^T from the resident
+    corpus (bit-identical to the frames' part on batch.frames()), followed by sv_lstm_weights_bf16."""
     sched = schedule_flags(schedule)
-    require_device(x, w_p, b_p, *[t for l in layers for t in l])
+    cb = _corpus_batch(x)
+    require_device(None if cb else x, w_p, b_p, *[t for l in layers for t in l])
     B, T, F = x.shape
     H = layers[0][1].shape[1]
     dev = x.device
@@ -364,10 +394,14 @@ def embedder_forward_bf16(x, layers, w_p, b_p, save=True, status=None, probe=Non
     st.T, st.B, st.H, st.P, st.bf16 = T, B, H, w_p.shape[0], True
     x_bf = _bf((T, B, F), dev)
     L = len(layers)
-    fused_x = F <= 64  # x -> time-major bf16 and x^T: in the weights' launch below (sv_lstm_prep_bf16)
+    # x -> time-major bf16 and x^T: in the weights' launch below (sv_lstm_prep_bf16)
+    fused_x = F <= 64 and not cb
     if save:  # layer 0's dW_ih operand x^T [F][T Bp] (padding columns zero)
-        st.xT0 = (torch.empty if fused_x or Bp == B else torch.zeros)((F, T * Bp), dtype=torch.bfloat16, device=dev)
-    if not fused_x:
+        st.xT0 = (torch.empty if cb or fused_x or Bp == B else torch.zeros)((F, T * Bp), dtype=torch.bfloat16,
+                                                                           device=dev)
+    if cb:
+        _corpus_prep("sv_corpus_batch_bf16", cb, x_bf, st.xT0, Bp, s)
+    elif not fused_x:
         x_tm = _f32((T, B, F), dev)
         call("sv_frames_to_time_major", ptr(x), ptr(x_tm), B, T, F, s)
         if save:

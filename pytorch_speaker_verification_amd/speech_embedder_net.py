@@ -16,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from ._lib import compute_device, loss_id
+from .data_load import CorpusBatch
 from .hparam import hparam as hp
 from .ops import EmbedderFunction, GE2EFunction
 from .utils import calc_loss, calc_loss_contrast, get_centroids, get_cossim  # noqa: F401  (re-exports, as :13)
@@ -83,6 +84,8 @@ class SpeechEmbedder(nn.Module):
 
     def forward(self, x):
         # x.float() (:28) -> LSTM -> last frame (:30) -> projection (:31) -> x/|x| (:32)
+        if isinstance(x, CorpusBatch):  # the autograd path takes the materialised batch
+            x = x.frames()
         params = self.flat_params()
         dev = compute_device(params[0])
         host = None if params[0].is_cuda else params[0].device

@@ -21,6 +21,13 @@
 Both take ``dataset=None``: a given dataset replaces the configured one -- the way to train or
 evaluate the reference's raw-waveform configuration (``data_preprocessed: false``) on decoded audio,
 with ``data_load.SpeakerDatasetWaveforms``, whose batches are made on the GPU and skip the pinned copy.
+
+A ``data_load.SpeakerDatasetResident`` (the preprocessed corpus kept on the device) is served by
+``data_load.ResidentBatches``: per step two int32 tables go to the device and the forward cuts its
+operands out of the corpus -- with the default arguments the host loader's batches, bit for bit and in
+its order.  ``train`` then also takes ``lengths`` (the frame counts T to draw from, one per batch;
+None = 160 always; ``data_load.batch_lengths`` gives the paper's [140, 180] on the GEMMs' fast grid),
+``crop`` ("head" | "random") and ``seed`` (of the private RNG both are drawn from).
 """
 from __future__ import annotations
 
@@ -33,7 +40,8 @@ import torch
 from torch.utils.data import DataLoader
 
 from ._lib import call, ptr, stream_of
-from .data_load import DevicePrefetcher, SpeakerDatasetTIMIT, SpeakerDatasetTIMITPreprocessed
+from .data_load import (TRAIN_FRAMES, DevicePrefetcher, ResidentBatches, SpeakerDatasetTIMIT,
+                        SpeakerDatasetTIMITPreprocessed)
 from .hparam import hparam as hp
 from .speech_embedder_net import GE2ELoss, SpeechEmbedder
 from .trainer import GE2ETrainer
@@ -53,16 +61,20 @@ def _value_neutral_perm(n):
 
 def _loader(dataset, split, pin_memory):
     """The reference's DataLoader (:26-27 / :97); a dataset whose items are already on the device
-    (on_device) is read in this process and not pinned."""
-    on_device = getattr(dataset, "on_device", False)
+    (on_device) is read in this process and not pinned, and so are a resident dataset's items (utterance
+    ids: its draws from the global RNG streams stay in this process)."""
+    on_device = getattr(dataset, "on_device", False) or getattr(dataset, "resident", False)
     return DataLoader(dataset, batch_size=split.N, shuffle=True, num_workers=0 if on_device else split.num_workers,
                       drop_last=True, pin_memory=pin_memory and not on_device)
 
 
-def train(model_path, dataset=None, loss_method="softmax"):
+def train(model_path, dataset=None, loss_method="softmax", lengths=None, crop="head", seed=0):
     device = torch.device(hp.device)
     train_dataset = _dataset() if dataset is None else dataset
     loader = _loader(train_dataset, hp.train, True)
+    resident = getattr(train_dataset, "resident", False)
+    if not resident and (lengths is not None or crop != "head"):
+        raise ValueError("train: lengths and crop need a resident dataset (data_load.SpeakerDatasetResident)")
     embedder_net = SpeechEmbedder().to(device)
     if hp.train.restore:
         embedder_net.load_state_dict(torch.load(model_path, weights_only=True))
@@ -73,11 +85,16 @@ def train(model_path, dataset=None, loss_method="softmax"):
     embedder_net.train()
     iteration = 0
     e = batch_id = 0
+    on_fetch = lambda: _value_neutral_perm(N * M)  # noqa: E731
+    if resident:  # one object for all epochs: its private RNG runs on
+        batches = ResidentBatches(loader, train_dataset.corpus, lengths, crop, seed, on_fetch=on_fetch)
     for e in range(hp.train.epochs):
         total_loss = torch.zeros((), device=device)
-        batches = DevicePrefetcher(loader, device, on_fetch=lambda: _value_neutral_perm(N * M))
+        if not resident:
+            batches = DevicePrefetcher(loader, device, on_fetch=on_fetch)
         for batch_id, mel_db_batch in enumerate(batches):
-            x = mel_db_batch.reshape(N * M, mel_db_batch.size(2), mel_db_batch.size(3))
+            # (a resident batch is N * M rows already)
+            x = mel_db_batch if resident else mel_db_batch.reshape(N * M, mel_db_batch.size(2), mel_db_batch.size(3))
             loss = trainer.step(x, N, M)
             total_loss = total_loss + loss
             iteration += 1
@@ -134,6 +151,10 @@ def test(model_path, dataset=None):
             batch_avg_EER = np.float32(0.0)
             batch_id = 0
             for batch_id, mel_db_batch in enumerate(loader):
+                if getattr(test_dataset, "resident", False):  # utterance ids [N, M] -> their first 160 frames
+                    ids = mel_db_batch.reshape(-1)
+                    mel_db_batch = test_dataset.corpus.frames(ids, torch.zeros_like(ids), TRAIN_FRAMES).reshape(
+                        N, M, TRAIN_FRAMES, -1)
                 mel = mel_db_batch.to(device)
                 enroll, verif = torch.split(mel, M // 2, dim=1)
                 enroll = enroll.reshape(N * M // 2, enroll.size(2), enroll.size(3))

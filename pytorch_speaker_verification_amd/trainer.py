@@ -42,6 +42,7 @@ import torch
 import torch.distributed as dist
 
 from ._lib import PersistStatus, call, ptr, stream_of
+from .data_load import CorpusBatch
 from .ops import clip_sgd_step2_, embedder_bwd, embedder_fwd
 from .sharded_ge2e import ShardedGE2E
 
@@ -161,7 +162,9 @@ class GE2ETrainer:
 
     def step(self, x, N, M, probe=None):
         """x: [N*M, T, nmels] float32 on this rank's GPU (this rank's N speakers x M
-        utterances, speaker-major).  Returns the (global) loss as a 0-dim device tensor.
+        utterances, speaker-major), or a data_load.CorpusBatch of that shape: the forward then cuts
+        its operands out of the resident corpus (the same step, bit for bit, as on x.frames(); T
+        may change from step to step).  Returns the (global) loss as a 0-dim device tensor.
         probe (bench only): {"fwd": events, "bwd": events, "kstamp": tensor} timing probes handed
         to the stack forward / backward (include/sv_ge2e.h)."""
         probe = probe or {}
@@ -177,16 +180,17 @@ class GE2ETrainer:
         schedule = getattr(net, "schedule", "auto")
         chunks = (bf16_row_chunks(x.shape[0], layers[0][1].shape[1], schedule, len(layers), x.shape[1], x.shape[2])
                   if bf16 else [(0, x.shape[0])])
+        resident = isinstance(x, CorpusBatch)  # its rows are table slices, its operands the kernel's
         if len(chunks) > 1:  # (bf16 only)
-            xf = x.float()
-            outs = [embedder_fwd(precision, xf[r0:r1].contiguous(), layers, w_p, b_p, status=self.status,
-                                 probe=probe.get("fwd") if i == 0 else None, schedule=schedule)
+            xf = x if resident else x.float()
+            outs = [embedder_fwd(precision, xf.rows(r0, r1) if resident else xf[r0:r1].contiguous(), layers, w_p, b_p,
+                                 status=self.status, probe=probe.get("fwd") if i == 0 else None, schedule=schedule)
                     for i, (r0, r1) in enumerate(chunks)]
             emb = torch.cat([o[0] for o in outs])
             st = [o[1] for o in outs]
         else:
-            emb, st = embedder_fwd(precision, x.float().contiguous(), layers, w_p, b_p, products=products,
-                                   status=self.status, probe=probe.get("fwd"), schedule=schedule)
+            emb, st = embedder_fwd(precision, x if resident else x.float().contiguous(), layers, w_p, b_p,
+                                   products=products, status=self.status, probe=probe.get("fwd"), schedule=schedule)
         E = emb.view(N, M, emb.shape[1])
         dp = self.dp
         # data parallel: the local loss partial goes to the head bucket's all-reduce (no collective)
