@@ -36,7 +36,7 @@ $(FAULT_LIB): $(FAULT_OBJ)
 # call un-ignores it): `make ab NAME=x FLAGS="-D..."` compiles every source with FLAGS into
 # scripts/ab/libsv_ge2e_x.so.  The sources keep only the phase-stamp builds as flags
 # (-DSV_PF32_STAMP [-DSV_PF32_WAVE_STAMP], -DSV_WB_STAMP, -DSV_WAVE3_STAMP: scripts/f32_step_ab.py
-# --stamps, scripts/wave_stamps.py); a candidate kernel change is an A/B build of a patched tree
+# --stamps, scripts/wave_stamps.py; -DSV_TRIAL_STAMP: scripts/trial_hist_bench.py --stamp-lib); a candidate kernel change is an A/B build of a patched tree
 # against `make ab NAME=base FLAGS=`, timed by scripts/gpu_ab.sh.  Variants measured slower are
 # deleted from the sources (DESIGN §4 keeps the record).
 NAME ?= ab

@@ -592,6 +592,32 @@ int sv_corpus_batch(const float* corpus, long n_utt, int F, int Tc, const int* u
 int sv_corpus_batch_bf16(const float* corpus, long n_utt, int F, int Tc, const int* utt, const int* start, int B,
                          int T, sv_bf16* x_bf, sv_bf16* xT, int Bp, hipStream_t stream);
 
+/* ---- verification trials (added under v12; additive): every pair of rows of two embedding
+ * matrices scored and binned in one launch, for a ROC over a whole held-out set (verification.py).
+ * The score matrix is never written: U utterances give U^2 / 2 scores, 20 GB at U = 100 000.
+ *   A [Na][lda], B [Nb][ldb] fp32 rows of D values, taken as they are (the caller normalises);
+ *   lab_a [Na], lab_b [Nb] device int32.  Pair (i, j) has the score s = sum_d A[i][d] B[j][d], fp32
+ *   products and sums on the exact fp32 MFMA.  A row with a negative label takes part in no pair; a
+ *   pair is a target when its two labels are equal, else a non-target.
+ *   symmetric != 0: B, ldb, lab_b, Nb must repeat A, lda, lab_a, Na; only the pairs i < j count.
+ *   Slot of a score, with q = floorf((s - lo) * inv_width) in two separately rounded fp32 operations:
+ *       slot 0             if !(q >= 0)     (below lo, or NaN)
+ *       slot n_bins + 1    if q >= n_bins
+ *       slot 1 + (int)q    otherwise
+ *   hist [2][n_bins + 2] unsigned 64-bit, sv_trial_hist_size(n_bins) bytes: row 0 non-targets, row 1
+ *   targets.  The kernel ADDS to it (64-bit atomics): the caller zeroes it, two calls accumulate.
+ *   Counts are integers, so the result depends neither on `grid` nor on arrival order.
+ *   grid: workgroups of the persistent launch, 0 = chosen from the device and the LDS footprint.
+ * One launch on `stream`, no workspace, nothing retained (sv_trials.hip has the tile plan).
+ * SV_EARG: a null pointer; Na, Nb, D or n_bins < 1; grid < 0; symmetric with different operands.
+ * SV_EALIGN: A or B off a 16-byte boundary (a label table off a 4-byte, hist off an 8-byte one);
+ * lda, ldb or D not a multiple of 4; lda or ldb < D.  SV_ESHAPE: n_bins > 8192; D > 1024.  Checked in
+ * that order, all before any launch. */
+size_t sv_trial_hist_size(int n_bins);
+int sv_trial_hist(const float* A, long lda, const int* lab_a, int Na, const float* B, long ldb, const int* lab_b,
+                  int Nb, int D, int symmetric, float lo, float inv_width, int n_bins, unsigned long long* hist,
+                  int grid, hipStream_t stream);
+
 /* ---- clip_grad_norm_ + SGD step over one flat parameter group (train_speech_embedder.py:63-65)
  * p -= lr * min(1, max_norm / (|g|_2 + 1e-6)) * g; write_grad=1 also scales g in place.
  * sync (may be NULL): a persistent-recurrence sync block; if its status is set the step is

@@ -28,6 +28,11 @@ operands out of the corpus -- with the default arguments the host loader's batch
 its order.  ``train`` then also takes ``lengths`` (the frame counts T to draw from, one per batch;
 None = 160 always; ``data_load.batch_lengths`` gives the paper's [140, 180] on the GEMMs' fast grid),
 ``crop`` ("head" | "random") and ``seed`` (of the private RNG both are drawn from).
+
+``test(..., protocol="corpus")`` (a resident dataset) runs ``verification.evaluate`` on the dataset's
+whole corpus instead -- every pair of utterances, one EER -- prints one line and returns that EER;
+``train(..., eval_corpus=corpus)`` runs it on ``corpus`` after every checkpoint and adds one line to
+stdout and the log file.  The default protocol and the existing log line are unchanged.
 """
 from __future__ import annotations
 
@@ -68,7 +73,7 @@ def _loader(dataset, split, pin_memory):
                       drop_last=True, pin_memory=pin_memory and not on_device)
 
 
-def train(model_path, dataset=None, loss_method="softmax", lengths=None, crop="head", seed=0):
+def train(model_path, dataset=None, loss_method="softmax", lengths=None, crop="head", seed=0, eval_corpus=None):
     device = torch.device(hp.device)
     train_dataset = _dataset() if dataset is None else dataset
     loader = _loader(train_dataset, hp.train, True)
@@ -109,6 +114,12 @@ def train(model_path, dataset=None, loss_method="softmax", lengths=None, crop="h
         if hp.train.checkpoint_dir is not None and (e + 1) % hp.train.checkpoint_interval == 0:
             ckpt = os.path.join(hp.train.checkpoint_dir, f"ckpt_epoch_{e + 1}_batch_id_{batch_id + 1}.pth")
             torch.save({k: v.detach().cpu() for k, v in embedder_net.state_dict().items()}, ckpt)
+            if eval_corpus is not None:
+                mesg = _corpus_line(embedder_net, eval_corpus, "Epoch:{0}\t".format(e + 1))
+                print(mesg)
+                if hp.train.log_file is not None:
+                    with open(hp.train.log_file, "a") as f:
+                        f.write(mesg)
     save_path = os.path.join(hp.train.checkpoint_dir, f"final_epoch_{e + 1}_batch_id_{batch_id + 1}.model")
     torch.save({k: v.detach().cpu() for k, v in embedder_net.state_dict().items()}, save_path)
     print("\nDone, trained model saved at", save_path)
@@ -136,9 +147,33 @@ def eer_from_sim(sim):
     return best
 
 
-def test(model_path, dataset=None):
+def _corpus_line(embedder_net, corpus, prefix=""):
+    """One line with verification.evaluate's figures on `corpus` (all pairs of its utterances)."""
+    from .verification import evaluate
+    with torch.no_grad():
+        r = evaluate(embedder_net, corpus)
+    return "{0}corpus EER:{1:.4f} [{2:.4f}, {3:.4f}]\tthres:{4:.4f}\tminDCF:{5:.4f}\ttrials:{6}+{7}\t\n".format(
+        prefix, r["eer"], r["eer_lo"], r["eer_hi"], r["threshold"], r["min_dcf"], r["n_target"], r["n_nontarget"])
+
+
+def test(model_path, dataset=None, protocol="batches"):
+    if protocol not in ("batches", "corpus"):
+        raise ValueError(f"unknown protocol {protocol!r} (expected 'batches' or 'corpus')")
     device = torch.device(hp.device)
     test_dataset = _dataset() if dataset is None else dataset
+    if protocol == "corpus":
+        if not getattr(test_dataset, "resident", False):
+            raise ValueError("test: protocol='corpus' needs a resident dataset (data_load.SpeakerDatasetResident)")
+        from .verification import evaluate
+        embedder_net = SpeechEmbedder()
+        embedder_net.load_state_dict(torch.load(model_path, weights_only=True))
+        embedder_net = embedder_net.to(device).eval()
+        with torch.no_grad():
+            r = evaluate(embedder_net, test_dataset.corpus)
+        print("\ncorpus EER : {0:.4f} in [{1:.4f}, {2:.4f}] (thres:{3:.4f}, minDCF:{4:.4f}, {5} target and {6} "
+              "non-target trials)".format(r["eer"], r["eer_lo"], r["eer_hi"], r["threshold"], r["min_dcf"],
+                                          r["n_target"], r["n_nontarget"]))
+        return float(r["eer"])
     loader = _loader(test_dataset, hp.test, False)
     embedder_net = SpeechEmbedder()
     embedder_net.load_state_dict(torch.load(model_path, weights_only=True))
