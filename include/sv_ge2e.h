@@ -618,6 +618,41 @@ int sv_trial_hist(const float* A, long lda, const int* lab_a, int Na, const floa
                   int Nb, int D, int symmetric, float lo, float inv_width, int n_bins, unsigned long long* hist,
                   int grid, hipStream_t stream);
 
+/* ---- adaptive score normalisation (AS-norm; added under v12; additive): the two device steps of
+ *     z(e, t) = 1/2 ((s - mu_e) / sigma_e + (s - mu_t) / sigma_t),
+ * mu_x, sigma_x the mean and standard deviation of the top_k largest scores of x against a cohort.
+ *
+ * sv_cohort_topk_stats: for every row i of X [N][ldx] the scores s_c = sum_d X[i][d] C[c][d] over the
+ * Nc rows of C [Nc][ldc], on the exact fp32 MFMA with sv_trial_hist's tile (a pair of rows scores the
+ * same bits in both); mean[i] = the mean of the top_k largest of them, std[i] = their population
+ * standard deviation (divisor top_k), both computed in fp64 from the fp32 scores and rounded once.
+ * The selection is exact, ties included: the top_k values are a multiset, so which of several equal
+ * scores is taken cannot matter.  It is a radix select (8-bit digits, 4 passes) on the order-preserving
+ * key of a score -- all 32 bits flipped if the sign bit is set, else the sign bit flipped -- plus one
+ * pass for the sums; each pass recomputes the scores, none is written, there is no workspace
+ * (sv_snorm.hip has the plan).  A NaN score takes the largest key, above +inf: a row of X with a NaN
+ * score gets NaN mean and std, and no other row is touched (a NaN row of C reaches every row).
+ *   grid: workgroups striding over the 128-row blocks of X, 0 = one per CU; the results do not depend
+ *   on it (the sums are combined in a fixed order).
+ * SV_EARG: a null pointer; N, Nc, D or top_k < 1; top_k > Nc; grid < 0.  SV_EALIGN: X or C off a
+ * 16-byte boundary (mean or std off a 4-byte one); ldx, ldc or D not a multiple of 4; ldx or ldc < D.
+ * SV_ESHAPE: Nc > 65 535 (16-bit bin counters); D > 1024.  Checked in that order, before the launch. */
+int sv_cohort_topk_stats(const float* X, long ldx, int N, const float* C, long ldc, int Nc, int D, int top_k,
+                         float* mean, float* std, int grid, hipStream_t stream);
+
+/* sv_trial_hist_norm: sv_trial_hist -- the same kernel, tiles, masks, labels, flush and `hist` -- with
+ * one step between the score s of pair (i, j) and the slot rule, five separately rounded fp32
+ * operations (no contraction):
+ *     za = (s - mu_a[i]) * inv_a[i];   zb = (s - mu_b[j]) * inv_b[j];   z = 0.5f * (za + zb);
+ * and the slot is sv_trial_hist's slot rule on z.  mu_a, inv_a [Na], mu_b, inv_b [Nb] device fp32 (inv
+ * is the caller's 1 / sigma, floored as the caller sees fit).  symmetric != 0 also requires
+ * mu_b == mu_a and inv_b == inv_a.  Errors as sv_trial_hist, in its order, with: a null mu / inv
+ * pointer or symmetric with different ones SV_EARG; one off a 4-byte boundary SV_EALIGN. */
+int sv_trial_hist_norm(const float* A, long lda, const int* lab_a, int Na, const float* B, long ldb, const int* lab_b,
+                       int Nb, int D, int symmetric, float lo, float inv_width, int n_bins, const float* mu_a,
+                       const float* inv_a, const float* mu_b, const float* inv_b, unsigned long long* hist, int grid,
+                       hipStream_t stream);
+
 /* ---- clip_grad_norm_ + SGD step over one flat parameter group (train_speech_embedder.py:63-65)
  * p -= lr * min(1, max_norm / (|g|_2 + 1e-6)) * g; write_grad=1 also scales g in place.
  * sync (may be NULL): a persistent-recurrence sync block; if its status is set the step is

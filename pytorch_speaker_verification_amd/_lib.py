@@ -162,6 +162,9 @@ SIGNATURES = {
     "sv_trial_hist_size": (_c_size_t, [_c_int]),
     "sv_trial_hist": (_c_int, [_P, _c_long, _P, _c_int, _P, _c_long, _P, _c_int, _c_int, _c_int, _c_float, _c_float,
                                _c_int, _P, _c_int, _P]),
+    "sv_cohort_topk_stats": (_c_int, [_P, _c_long, _c_int, _P, _c_long, _c_int, _c_int, _c_int, _P, _P, _c_int, _P]),
+    "sv_trial_hist_norm": (_c_int, [_P, _c_long, _P, _c_int, _P, _c_long, _P, _c_int, _c_int, _c_int, _c_float,
+                                    _c_float, _c_int, _P, _P, _P, _P, _P, _c_int, _P]),
     "sv_clip_sgd_workspace": (_c_size_t, []),
     "sv_clip_sgd_step": (_c_int, [_P, _P, _c_long, _c_float, _c_float, _c_int, _P, _P, _P, _P]),
     "sv_clip_sgd_step2": (_c_int, [_P, _P, _c_long, _c_float, _P, _P, _c_long, _c_float, _c_float, _c_int, _P, _P, _P,

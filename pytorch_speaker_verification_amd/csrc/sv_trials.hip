@@ -22,23 +22,25 @@
 //   LDS      2 * 32 * 132 * 4 = 33 792 B of operands + 1 KB of labels + 8 (n_bins + 2) B of
 //            histograms: 100 368 B at the limit n_bins = 8192 (one workgroup per CU), 67 600 B at the
 //            default 4096 (two per CU: one's epilogue runs under the other's MFMAs).
-// Counts are integers: the result does not depend on the grid or on arrival order.
+//   norm     sv_trial_hist_norm is the same kernel with NORM = true: the score passes through the
+//            normalisation step of include/sv_ge2e.h on its way to the slot rule, and mu and inv of
+//            the tile's 128 + 128 rows are staged beside the labels (2 KB more LDS: 69 648 B at 4096
+//            bins, still two workgroups per CU).
+// Counts are integers: the result does not depend on the grid or on arrival order.  The tile's k-loop
+// and operand staging are in sv_trial_tile.h, shared with sv_snorm.hip.
 // -DSV_TRIAL_STAMP (an A/B build, never the shipped library): two more 64-bit words behind the
 // histogram take wave 0's cycles inside the k-loops and inside the epilogues, summed over workgroups.
-#include "sv_common.h"
+#include "sv_trial_tile.h"
 #include "../../include/sv_ge2e.h"
 
 #include <algorithm>
 
 namespace {
 
-constexpr int TR_T = 128;       // tile edge (pairs)
-constexpr int TR_KC = 32;       // operand columns per chunk
-constexpr int TR_LD = TR_T + 4; // LDS row stride of one k (floats)
-constexpr int TR_NLD = TR_T * TR_KC / 4 / 256;  // 16-byte loads per thread and operand per chunk
 constexpr int TR_FLUSH = 256;   // tiles between two flushes (bound: 2^18, see above)
-constexpr int TR_MAX_BINS = 8192, TR_MAX_D = 1024;
-constexpr size_t TR_LDS_FIXED = (size_t)(2 * TR_KC * TR_LD + 2 * TR_T) * 4;
+constexpr int TR_MAX_BINS = 8192;
+constexpr size_t TR_LDS_FIXED = (size_t)(TR_OPERAND_FLOATS + 2 * TR_T) * 4;
+constexpr size_t TR_LDS_NORM = (size_t)4 * TR_T * 4;  // NORM: mu and inv of the tile's A rows and B rows
 
 struct TrialArgs {
   const float *A, *B;
@@ -49,6 +51,7 @@ struct TrialArgs {
   long long n_tiles;
   int ntb;  // tile columns (rectangular mode)
   unsigned long long* hist;
+  const float *mu_a, *inv_a, *mu_b, *inv_b;  // sv_trial_hist_norm only
 };
 
 // the slot rule of include/sv_ge2e.h: two separately rounded fp32 operations, then floorf; the three
@@ -59,52 +62,70 @@ __device__ __forceinline__ int trial_slot(float s, float lo, float inv_width, fl
   return (int)fminf(fmaxf(q + 1.f, 0.f), top);
 }
 
-// one wave's 64 x 64 scores into the workgroup's histograms.  The row labels are read before the
-// first atomic (the compiler cannot move an LDS read across one); DIAG: a diagonal tile of the
-// symmetric mode, where only row < col counts
-template <bool DIAG>
-__device__ __forceinline__ void trial_bin(const f32x16 (&acc)[4], const int* __restrict__ labs, unsigned* __restrict__ hs,
-                                          int wr, int wc, int lane, float lo, float inv_width, int n_bins) {
-  int la[2][16];
+// the score-normalisation step of sv_trial_hist_norm (include/sv_ge2e.h): four separately rounded
+// fp32 operations, then the factor 0.5 (exact short of underflow)
+__device__ __forceinline__ float trial_norm(float s, float mu_a, float inv_a, float mu_b, float inv_b) {
+  const float za = __fmul_rn(__fsub_rn(s, mu_a), inv_a), zb = __fmul_rn(__fsub_rn(s, mu_b), inv_b);
+  return __fmul_rn(0.5f, __fadd_rn(za, zb));
+}
+
+// one wave's scores into the workgroup's histograms, the NB 32-row accumulator blocks from B0 on.
+// The rows' labels -- and with NORM their mu and inv, nrm = [mu_a | inv_a | mu_b | inv_b] of the
+// tile's rows -- are read before the first atomic (the compiler cannot move an LDS read across one);
+// DIAG: a diagonal tile of the symmetric mode, where only row < col counts
+template <bool DIAG, bool NORM, int B0, int NB>
+__device__ __forceinline__ void trial_bin_rows(const f32x16 (&acc)[4], const int* __restrict__ labs,
+                                               const float* __restrict__ nrm, unsigned* __restrict__ hs, int wr,
+                                               int wc, int lane, float lo, float inv_width, int n_bins) {
+  int la[NB][16];
+  float mu[NORM ? NB : 1][16], iv[NORM ? NB : 1][16], mub[2], ivb[2];
 #pragma unroll
-  for (int bi = 0; bi < 2; ++bi)
+  for (int bi = 0; bi < NB; ++bi)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) la[bi][r] = labs[wr + bi * 32 + acc_row(r, lane)];
+    for (int r = 0; r < 16; ++r) {
+      const int row = wr + (B0 + bi) * 32 + acc_row(r, lane);
+      la[bi][r] = labs[row];
+      if constexpr (NORM) {
+        mu[bi][r] = nrm[row];
+        iv[bi][r] = nrm[TR_T + row];
+      }
+    }
+  if constexpr (NORM)
+#pragma unroll
+    for (int bj = 0; bj < 2; ++bj) {
+      mub[bj] = nrm[2 * TR_T + wc + bj * 32 + (lane & 31)];
+      ivb[bj] = nrm[3 * TR_T + wc + bj * 32 + (lane & 31)];
+    }
   const float top = (float)(n_bins + 1);
 #pragma unroll
-  for (int b = 0; b < 4; ++b) {
+  for (int b = 2 * B0; b < 2 * (B0 + NB); ++b) {
     const int col = wc + (b & 1) * 32 + (lane & 31);
     const int lb = labs[TR_T + col];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int l = la[b >> 1][r];
+      const int l = la[(b >> 1) - B0][r];
       bool live = (l | lb) >= 0;  // neither label negative
       if constexpr (DIAG) live = live && wr + (b >> 1) * 32 + acc_row(r, lane) < col;
-      if (live) atomicAdd(hs + (l == lb ? n_bins + 2 : 0) + trial_slot(acc[b][r], lo, inv_width, top), 1u);
+      float s = acc[b][r];
+      if constexpr (NORM) s = trial_norm(s, mu[(b >> 1) - B0][r], iv[(b >> 1) - B0][r], mub[b & 1], ivb[b & 1]);
+      if (live) atomicAdd(hs + (l == lb ? n_bins + 2 : 0) + trial_slot(s, lo, inv_width, top), 1u);
     }
   }
 }
 
-__device__ __forceinline__ void trial_load(const float* __restrict__ P, long ld, int N, int D, long row0, int k0,
-                                           int tid, f32x4 (&v)[TR_NLD]) {
-#pragma unroll
-  for (int p = 0; p < TR_NLD; ++p) {
-    const int f = tid + p * 256;
-    const long row = row0 + (f >> 3);
-    const int k = k0 + (f & 7) * 4;
-    v[p] = (row < N && k < D) ? *reinterpret_cast<const f32x4*>(P + row * ld + k) : f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-}
-
-__device__ __forceinline__ void trial_store(float* __restrict__ S, int tid, const f32x4 (&v)[TR_NLD]) {
-#pragma unroll
-  for (int p = 0; p < TR_NLD; ++p) {
-    const int f = tid + p * 256;
-    float* dst = S + (f & 7) * 4 * TR_LD + (f >> 3);
-    dst[0] = v[p].x;
-    dst[TR_LD] = v[p].y;
-    dst[2 * TR_LD] = v[p].z;
-    dst[3 * TR_LD] = v[p].w;
+// one wave's 64 x 64 scores.  Plain: all 32 row labels ahead of the first atomic.  NORM: the two
+// 32-row halves one after the other, each with its 16 labels, mu and inv per lane ahead of its
+// atomics -- 48 table registers instead of 96 keep the kernel at two waves per SIMD, for one more
+// exposed LDS read latency per tile
+template <bool DIAG, bool NORM>
+__device__ __forceinline__ void trial_bin(const f32x16 (&acc)[4], const int* __restrict__ labs,
+                                          const float* __restrict__ nrm, unsigned* __restrict__ hs, int wr, int wc,
+                                          int lane, float lo, float inv_width, int n_bins) {
+  if constexpr (NORM) {
+    trial_bin_rows<DIAG, true, 0, 1>(acc, labs, nrm, hs, wr, wc, lane, lo, inv_width, n_bins);
+    trial_bin_rows<DIAG, true, 1, 1>(acc, labs, nrm, hs, wr, wc, lane, lo, inv_width, n_bins);
+  } else {
+    trial_bin_rows<DIAG, false, 0, 2>(acc, labs, nrm, hs, wr, wc, lane, lo, inv_width, n_bins);
   }
 }
 
@@ -122,12 +143,16 @@ __device__ __forceinline__ void trial_flush(unsigned* __restrict__ hs, unsigned 
   __syncthreads();
 }
 
+// NORM: sv_trial_hist_norm -- the score takes the normalisation step on its way to the slot rule,
+// and the tile's per-row constants are staged beside the labels
+template <bool NORM>
 __global__ __launch_bounds__(256) void trial_hist_kernel(const TrialArgs a) {
   extern __shared__ float lds[];
   float* As = lds;
   float* Bs = As + TR_KC * TR_LD;
-  int* labs = reinterpret_cast<int*>(Bs + TR_KC * TR_LD);  // [0, 128) rows of A, [128, 256) rows of B
-  unsigned* hs = reinterpret_cast<unsigned*>(labs + 2 * TR_T);
+  int* labs = reinterpret_cast<int*>(lds + TR_OPERAND_FLOATS);  // [0, 128) rows of A, [128, 256) rows of B
+  float* nrm = reinterpret_cast<float*>(labs + 2 * TR_T);       // NORM: [mu_a | inv_a | mu_b | inv_b]
+  unsigned* hs = reinterpret_cast<unsigned*>(nrm + (NORM ? 4 * TR_T : 0));
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = (wave >> 1) * 64, wc = (wave & 1) * 64;
   const int n_slots = 2 * (a.n_bins + 2);
@@ -152,46 +177,23 @@ __global__ __launch_bounds__(256) void trial_hist_kernel(const TrialArgs a) {
     const long long c0 = clock64();
 #endif
     f32x16 acc[4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
-    f32x4 va[TR_NLD], vb[TR_NLD];
-    trial_load(a.A, a.lda, a.Na, a.D, i0, 0, tid, va);
-    trial_load(a.B, a.ldb, a.Nb, a.D, j0, 0, tid, vb);
-    for (int k0 = 0; k0 < a.D; k0 += TR_KC) {
-      __syncthreads();  // the last chunk's reads, and the last tile's label reads, are done
-      trial_store(As, tid, va);
-      trial_store(Bs, tid, vb);
-      if (k0 == 0) {
-        const long g = (tid < TR_T ? i0 : j0 - TR_T) + tid;
-        const int n = tid < TR_T ? a.Na : a.Nb;
-        labs[tid] = g < n ? (tid < TR_T ? a.lab_a : a.lab_b)[g] : -1;
+    trial_tile_scores(acc, a.A, a.lda, a.Na, i0, a.B, a.ldb, a.Nb, j0, a.D, As, Bs, tid, lane, wr, wc, [&] {
+      const bool rows_a = tid < TR_T;
+      const long g = (rows_a ? i0 : j0 - TR_T) + tid;
+      const bool in = g < (rows_a ? a.Na : a.Nb);
+      labs[tid] = in ? (rows_a ? a.lab_a : a.lab_b)[g] : -1;
+      if constexpr (NORM) {  // (a row outside is in no pair: its constants are never used)
+        nrm[(rows_a ? 0 : TR_T) + tid] = in ? (rows_a ? a.mu_a : a.mu_b)[g] : 0.f;
+        nrm[(rows_a ? TR_T : 2 * TR_T) + tid] = in ? (rows_a ? a.inv_a : a.inv_b)[g] : 0.f;
       }
-      __syncthreads();
-      if (k0 + TR_KC < a.D) {
-        trial_load(a.A, a.lda, a.Na, a.D, i0, k0 + TR_KC, tid, va);
-        trial_load(a.B, a.ldb, a.Nb, a.D, j0, k0 + TR_KC, tid, vb);
-      }
-      const float* ap = As + (lane >> 5) * TR_LD + wr + (lane & 31);
-      const float* bp = Bs + (lane >> 5) * TR_LD + wc + (lane & 31);
-#pragma unroll
-      for (int kk = 0; kk < TR_KC / 2; ++kk) {
-        const float a0 = ap[2 * kk * TR_LD], a1 = ap[2 * kk * TR_LD + 32];
-        const float b0 = bp[2 * kk * TR_LD], b1 = bp[2 * kk * TR_LD + 32];
-        acc[0] = mfma32x32x2(a0, b0, acc[0]);
-        acc[1] = mfma32x32x2(a0, b1, acc[1]);
-        acc[2] = mfma32x32x2(a1, b0, acc[2]);
-        acc[3] = mfma32x32x2(a1, b1, acc[3]);
-      }
-    }
+    });
 #ifdef SV_TRIAL_STAMP
     const long long c1 = clock64();
 #endif
     if (a.symmetric && ti == tj)
-      trial_bin<true>(acc, labs, hs, wr, wc, lane, a.lo, a.inv_width, a.n_bins);
+      trial_bin<true, NORM>(acc, labs, nrm, hs, wr, wc, lane, a.lo, a.inv_width, a.n_bins);
     else
-      trial_bin<false>(acc, labs, hs, wr, wc, lane, a.lo, a.inv_width, a.n_bins);
+      trial_bin<false, NORM>(acc, labs, nrm, hs, wr, wc, lane, a.lo, a.inv_width, a.n_bins);
 #ifdef SV_TRIAL_STAMP
     const long long c2 = clock64();
     cyc_k += c1 - c0;
@@ -211,6 +213,38 @@ __global__ __launch_bounds__(256) void trial_hist_kernel(const TrialArgs a) {
 #endif
 }
 
+// the checks and the launch of both entry points; nrm: {mu_a, inv_a, mu_b, inv_b} or NULL
+int trial_hist_launch(const float* A, long lda, const int* lab_a, int Na, const float* B, long ldb, const int* lab_b,
+                      int Nb, int D, int symmetric, float lo, float inv_width, int n_bins,
+                      const float* const* nrm, unsigned long long* hist, int grid, hipStream_t stream) {
+  if (!A || !B || !lab_a || !lab_b || !hist || Na < 1 || Nb < 1 || D < 1 || n_bins < 1 || grid < 0) return SV_EARG;
+  if (nrm && (!nrm[0] || !nrm[1] || !nrm[2] || !nrm[3])) return SV_EARG;
+  if (symmetric && (A != B || lab_a != lab_b || Na != Nb || lda != ldb)) return SV_EARG;
+  if (symmetric && nrm && (nrm[0] != nrm[2] || nrm[1] != nrm[3])) return SV_EARG;
+  if ((((uintptr_t)A | (uintptr_t)B) & 15) || (((uintptr_t)lab_a | (uintptr_t)lab_b) & 3) || ((uintptr_t)hist & 7) ||
+      lda % 4 || ldb % 4 || D % 4 || lda < D || ldb < D)
+    return SV_EALIGN;
+  if (nrm && (((uintptr_t)nrm[0] | (uintptr_t)nrm[1] | (uintptr_t)nrm[2] | (uintptr_t)nrm[3]) & 3)) return SV_EALIGN;
+  if (n_bins > TR_MAX_BINS || D > TR_MAX_D) return SV_ESHAPE;
+  const long long nta = ((long long)Na + TR_T - 1) / TR_T, ntb = ((long long)Nb + TR_T - 1) / TR_T;
+  TrialArgs a{A, B, lab_a, lab_b, lda, ldb, Na, Nb, D, symmetric != 0, n_bins, lo, inv_width,
+              symmetric ? nta * (nta + 1) / 2 : nta * ntb, (int)ntb, hist,
+              nrm ? nrm[0] : nullptr, nrm ? nrm[1] : nullptr, nrm ? nrm[2] : nullptr, nrm ? nrm[3] : nullptr};
+  const size_t lds = TR_LDS_FIXED + (nrm ? TR_LDS_NORM : 0) + 2 * ((size_t)n_bins + 2) * 4;
+  if (grid == 0) {  // every CU busy; two workgroups on each where the histograms leave room for them
+    const int cus = sv_stream_cus(stream);
+    const int per_cu = 2 * lds <= 160 * 1024 ? 2 : 1;
+    grid = (int)std::min<long long>(a.n_tiles, (long long)(cus > 0 ? cus : 256) * per_cu);
+  }
+  grid = (int)std::min<long long>(grid, a.n_tiles);
+  if (nrm)
+    hipLaunchKernelGGL(trial_hist_kernel<true>, dim3(grid), dim3(256), lds, stream, a);
+  else
+    hipLaunchKernelGGL(trial_hist_kernel<false>, dim3(grid), dim3(256), lds, stream, a);
+  SV_LAUNCH_CHECK();
+  return SV_OK;
+}
+
 }  // namespace
 
 extern "C" size_t sv_trial_hist_size(int n_bins) {
@@ -225,23 +259,15 @@ extern "C" size_t sv_trial_hist_size(int n_bins) {
 extern "C" int sv_trial_hist(const float* A, long lda, const int* lab_a, int Na, const float* B, long ldb,
                              const int* lab_b, int Nb, int D, int symmetric, float lo, float inv_width, int n_bins,
                              unsigned long long* hist, int grid, hipStream_t stream) {
-  if (!A || !B || !lab_a || !lab_b || !hist || Na < 1 || Nb < 1 || D < 1 || n_bins < 1 || grid < 0) return SV_EARG;
-  if (symmetric && (A != B || lab_a != lab_b || Na != Nb || lda != ldb)) return SV_EARG;
-  if ((((uintptr_t)A | (uintptr_t)B) & 15) || (((uintptr_t)lab_a | (uintptr_t)lab_b) & 3) || ((uintptr_t)hist & 7) ||
-      lda % 4 || ldb % 4 || D % 4 || lda < D || ldb < D)
-    return SV_EALIGN;
-  if (n_bins > TR_MAX_BINS || D > TR_MAX_D) return SV_ESHAPE;
-  const long long nta = ((long long)Na + TR_T - 1) / TR_T, ntb = ((long long)Nb + TR_T - 1) / TR_T;
-  TrialArgs a{A, B, lab_a, lab_b, lda, ldb, Na, Nb, D, symmetric != 0, n_bins, lo, inv_width,
-              symmetric ? nta * (nta + 1) / 2 : nta * ntb, (int)ntb, hist};
-  const size_t lds = TR_LDS_FIXED + 2 * ((size_t)n_bins + 2) * 4;
-  if (grid == 0) {  // every CU busy; two workgroups on each where the histograms leave room for them
-    const int cus = sv_stream_cus(stream);
-    const int per_cu = 2 * lds <= 160 * 1024 ? 2 : 1;
-    grid = (int)std::min<long long>(a.n_tiles, (long long)(cus > 0 ? cus : 256) * per_cu);
-  }
-  grid = (int)std::min<long long>(grid, a.n_tiles);
-  hipLaunchKernelGGL(trial_hist_kernel, dim3(grid), dim3(256), lds, stream, a);
-  SV_LAUNCH_CHECK();
-  return SV_OK;
+  return trial_hist_launch(A, lda, lab_a, Na, B, ldb, lab_b, Nb, D, symmetric, lo, inv_width, n_bins, nullptr, hist,
+                           grid, stream);
+}
+
+extern "C" int sv_trial_hist_norm(const float* A, long lda, const int* lab_a, int Na, const float* B, long ldb,
+                                  const int* lab_b, int Nb, int D, int symmetric, float lo, float inv_width,
+                                  int n_bins, const float* mu_a, const float* inv_a, const float* mu_b,
+                                  const float* inv_b, unsigned long long* hist, int grid, hipStream_t stream) {
+  const float* nrm[4] = {mu_a, inv_a, mu_b, inv_b};
+  return trial_hist_launch(A, lda, lab_a, Na, B, ldb, lab_b, Nb, D, symmetric, lo, inv_width, n_bins, nrm, hist, grid,
+                           stream);
 }

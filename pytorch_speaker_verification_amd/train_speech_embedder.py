@@ -33,6 +33,11 @@ None = 160 always; ``data_load.batch_lengths`` gives the paper's [140, 180] on t
 whole corpus instead -- every pair of utterances, one EER -- prints one line and returns that EER;
 ``train(..., eval_corpus=corpus)`` runs it on ``corpus`` after every checkpoint and adds one line to
 stdout and the log file.  The default protocol and the existing log line are unchanged.
+
+``test(..., protocol="corpus", cohort=c, top_k=k)`` and ``train(..., eval_corpus=corpus, eval_cohort=c,
+eval_top_k=k)`` hand a cohort to ``evaluate``: the figures are then those of the AS-normalised scores
+(adaptive symmetric score normalisation, verification.py), and the line says so.  The cohort -- a
+DeviceCorpus or a tensor of unit speaker models -- must not contain the evaluated speakers.
 """
 from __future__ import annotations
 
@@ -73,7 +78,10 @@ def _loader(dataset, split, pin_memory):
                       drop_last=True, pin_memory=pin_memory and not on_device)
 
 
-def train(model_path, dataset=None, loss_method="softmax", lengths=None, crop="head", seed=0, eval_corpus=None):
+def train(model_path, dataset=None, loss_method="softmax", lengths=None, crop="head", seed=0, eval_corpus=None,
+          eval_cohort=None, eval_top_k=300):
+    if eval_cohort is not None and eval_corpus is None:
+        raise ValueError("train: eval_cohort needs eval_corpus")
     device = torch.device(hp.device)
     train_dataset = _dataset() if dataset is None else dataset
     loader = _loader(train_dataset, hp.train, True)
@@ -115,7 +123,7 @@ def train(model_path, dataset=None, loss_method="softmax", lengths=None, crop="h
             ckpt = os.path.join(hp.train.checkpoint_dir, f"ckpt_epoch_{e + 1}_batch_id_{batch_id + 1}.pth")
             torch.save({k: v.detach().cpu() for k, v in embedder_net.state_dict().items()}, ckpt)
             if eval_corpus is not None:
-                mesg = _corpus_line(embedder_net, eval_corpus, "Epoch:{0}\t".format(e + 1))
+                mesg = _corpus_line(embedder_net, eval_corpus, "Epoch:{0}\t".format(e + 1), eval_cohort, eval_top_k)
                 print(mesg)
                 if hp.train.log_file is not None:
                     with open(hp.train.log_file, "a") as f:
@@ -147,18 +155,26 @@ def eer_from_sim(sim):
     return best
 
 
-def _corpus_line(embedder_net, corpus, prefix=""):
-    """One line with verification.evaluate's figures on `corpus` (all pairs of its utterances)."""
+def _as_norm_note(r):
+    return "AS-norm top {0} of {1}".format(r["top_k"], r["n_cohort"]) if "score_norm" in r else ""
+
+
+def _corpus_line(embedder_net, corpus, prefix="", cohort=None, top_k=300):
+    """One line with verification.evaluate's figures on `corpus` (all pairs of its utterances; with a
+    cohort those of the AS-normalised scores, and one more field that says so)."""
     from .verification import evaluate
     with torch.no_grad():
-        r = evaluate(embedder_net, corpus)
-    return "{0}corpus EER:{1:.4f} [{2:.4f}, {3:.4f}]\tthres:{4:.4f}\tminDCF:{5:.4f}\ttrials:{6}+{7}\t\n".format(
-        prefix, r["eer"], r["eer_lo"], r["eer_hi"], r["threshold"], r["min_dcf"], r["n_target"], r["n_nontarget"])
+        r = evaluate(embedder_net, corpus, cohort=cohort, top_k=top_k)
+    return "{0}corpus EER:{1:.4f} [{2:.4f}, {3:.4f}]\tthres:{4:.4f}\tminDCF:{5:.4f}\ttrials:{6}+{7}\t{8}\n".format(
+        prefix, r["eer"], r["eer_lo"], r["eer_hi"], r["threshold"], r["min_dcf"], r["n_target"], r["n_nontarget"],
+        _as_norm_note(r) + "\t" if cohort is not None else "")
 
 
-def test(model_path, dataset=None, protocol="batches"):
+def test(model_path, dataset=None, protocol="batches", cohort=None, top_k=300):
     if protocol not in ("batches", "corpus"):
         raise ValueError(f"unknown protocol {protocol!r} (expected 'batches' or 'corpus')")
+    if cohort is not None and protocol != "corpus":
+        raise ValueError("test: a cohort (AS-norm) needs protocol='corpus'")
     device = torch.device(hp.device)
     test_dataset = _dataset() if dataset is None else dataset
     if protocol == "corpus":
@@ -169,10 +185,11 @@ def test(model_path, dataset=None, protocol="batches"):
         embedder_net.load_state_dict(torch.load(model_path, weights_only=True))
         embedder_net = embedder_net.to(device).eval()
         with torch.no_grad():
-            r = evaluate(embedder_net, test_dataset.corpus)
+            r = evaluate(embedder_net, test_dataset.corpus, cohort=cohort, top_k=top_k)
         print("\ncorpus EER : {0:.4f} in [{1:.4f}, {2:.4f}] (thres:{3:.4f}, minDCF:{4:.4f}, {5} target and {6} "
-              "non-target trials)".format(r["eer"], r["eer_lo"], r["eer_hi"], r["threshold"], r["min_dcf"],
-                                          r["n_target"], r["n_nontarget"]))
+              "non-target trials{7})".format(r["eer"], r["eer_lo"], r["eer_hi"], r["threshold"], r["min_dcf"],
+                                             r["n_target"], r["n_nontarget"],
+                                             ", " + _as_norm_note(r) if cohort is not None else ""))
         return float(r["eer"])
     loader = _loader(test_dataset, hp.test, False)
     embedder_net = SpeechEmbedder()

@@ -8,6 +8,10 @@ bins every fp32 dot product in the epilogue of the scoring GEMM into a target an
 histogram (U utterances give U^2 / 2 trials; at U = 100 000 the score matrix would be 20 GB).
 
   trial_histograms   the kernel: two histograms of all pairs of rows of one or two matrices
+  cohort_stats       mean and std of every row's top-K scores against a cohort (sv_cohort_topk_stats)
+  cohort_models, as_norm, norm_range
+                     adaptive score normalisation (AS-norm): the usual cohort, a trial side's (mu, 1 / sigma),
+                     and the range of the normalised score that the first histogram pass covers
   roc, eer, min_dcf  FAR / FRR at the bin edges, the equal error rate with an interval that
                      contains the sorted-scores EER, the normalised minimum detection cost
   corpus_eer         histogram passes that zoom into the FAR / FRR crossing
@@ -28,6 +32,7 @@ from ._lib import call, lib, ptr, stream_of
 from .data_load import TRAIN_FRAMES, CorpusBatch
 
 MAX_BINS, MAX_D = 8192, 1024  # include/sv_ge2e.h: sv_trial_hist's SV_ESHAPE limits
+MAX_COHORT = 65535             # sv_cohort_topk_stats' (16-bit bin counters)
 
 
 class TrialHist:
@@ -84,15 +89,35 @@ def _labels(lab, n, dev, name):
     return lab.contiguous()
 
 
-def trial_histograms(a, lab_a, b=None, lab_b=None, bins=4096, lo=-1.0, hi=1.0, grid=0):
+def _norm(norm, n, dev, name):
+    """(mu, inv) of one trial side as float32 [n] contiguous tensors on dev."""
+    try:
+        mu, inv = norm
+    except (TypeError, ValueError):
+        raise ValueError(f"trial_histograms: {name} must be a pair (mu, inv)") from None
+    for t in (mu, inv):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != dev or t.shape != (n,):
+            raise ValueError(f"trial_histograms: {name} must hold two float32 [{n}] tensors on {dev}")
+    return mu.contiguous(), inv.contiguous()
+
+
+def trial_histograms(a, lab_a, b=None, lab_b=None, bins=4096, lo=-1.0, hi=1.0, grid=0, norm_a=None, norm_b=None):
     """The histograms of s = a[i] . b[j] over all pairs (sv_trial_hist, include/sv_ge2e.h has the slot
     rule): a [Na, D], b [Nb, D] float32 device tensors -- rows may be strided views -- with int32 labels
     on the same device; a pair is a target when its labels are equal, and a row with a negative label
     takes part in no pair.  b=None is the symmetric mode: the pairs i < j of a alone.  grid: the
     number of workgroups, 0 = automatic (the counts do not depend on it).  Returns a TrialHist on
-    the host.  Raises on CPU tensors: there is no CPU path."""
+    the host.  Raises on CPU tensors: there is no CPU path.
+
+    norm_a = (mu, inv), float32 [Na] each (and norm_b for b; in symmetric mode norm_a serves both
+    sides): the histograms of z = 0.5 ((s - mu_a[i]) inv_a[i] + (s - mu_b[j]) inv_b[j]) instead
+    (sv_trial_hist_norm; as_norm makes the pairs).  [lo, hi) is then a range of z: norm_range."""
     if (b is None) != (lab_b is None):
         raise ValueError("trial_histograms: give b and lab_b together, or neither (symmetric mode)")
+    if b is None and norm_b is not None:
+        raise ValueError("trial_histograms: the symmetric mode takes norm_a for both sides")
+    if b is not None and (norm_a is None) != (norm_b is None):
+        raise ValueError("trial_histograms: give norm_a and norm_b together, or neither")
     bins = int(bins)
     if not 1 <= bins <= MAX_BINS:
         raise ValueError(f"trial_histograms: bins = {bins} outside [1, {MAX_BINS}]")
@@ -108,11 +133,77 @@ def trial_histograms(a, lab_a, b=None, lab_b=None, bins=4096, lo=-1.0, hi=1.0, g
             raise ValueError(f"trial_histograms: a {tuple(a.shape)} on {a.device} and b {tuple(b.shape)} on {b.device} "
                              "differ in D or device")
         lab_b = _labels(lab_b, b.shape[0], a.device, "lab_b")
+    if norm_a is not None:
+        norm_a = _norm(norm_a, a.shape[0], a.device, "norm_a")
+        norm_b = norm_a if symmetric else _norm(norm_b, b.shape[0], a.device, "norm_b")
     with torch.cuda.device(a.device):
         hist = torch.zeros(int(lib().sv_trial_hist_size(bins)) // 8, dtype=torch.int64, device=a.device)
-        call("sv_trial_hist", ptr(a), a.stride(0), ptr(lab_a), a.shape[0], ptr(b), b.stride(0), ptr(lab_b), b.shape[0],
-             a.shape[1], int(symmetric), float(lo32), float(inv_width), bins, ptr(hist), int(grid), stream_of(a))
+        if norm_a is None:
+            call("sv_trial_hist", ptr(a), a.stride(0), ptr(lab_a), a.shape[0], ptr(b), b.stride(0), ptr(lab_b),
+                 b.shape[0], a.shape[1], int(symmetric), float(lo32), float(inv_width), bins, ptr(hist), int(grid),
+                 stream_of(a))
+        else:
+            call("sv_trial_hist_norm", ptr(a), a.stride(0), ptr(lab_a), a.shape[0], ptr(b), b.stride(0), ptr(lab_b),
+                 b.shape[0], a.shape[1], int(symmetric), float(lo32), float(inv_width), bins, ptr(norm_a[0]),
+                 ptr(norm_a[1]), ptr(norm_b[0]), ptr(norm_b[1]), ptr(hist), int(grid), stream_of(a))
     return TrialHist(hist[:2 * (bins + 2)].view(2, bins + 2).cpu().numpy(), lo32, hi32, bins)
+
+
+# ----------------------------------------------------------------------------- AS-norm
+def cohort_stats(x, cohort, top_k, grid=0):
+    """(mean, std), float32 [N] on the device: for every row of x [N, D] the mean and the population
+    standard deviation (divisor top_k) of the top_k largest of its scores x[i] . cohort[c] over the rows
+    of cohort [Nc, D] (sv_cohort_topk_stats: an exact radix select inside the scoring GEMM, no score
+    written).  Operands as trial_histograms' (float32 device tensors, rows may be strided views);
+    Nc <= 65 535.  A row with a NaN score gets NaN.  grid: the number of workgroups, 0 = automatic
+    (the results do not depend on it).  ValueError for top_k outside [1, Nc]."""
+    x, cohort = _rows(x, "x"), _rows(cohort, "cohort")
+    if cohort.device != x.device or cohort.shape[1] != x.shape[1]:
+        raise ValueError(f"cohort_stats: x {tuple(x.shape)} on {x.device} and cohort {tuple(cohort.shape)} on "
+                         f"{cohort.device} differ in D or device")
+    n, nc, top_k = x.shape[0], cohort.shape[0], int(top_k)
+    if nc > MAX_COHORT:
+        raise ValueError(f"cohort_stats: {nc} cohort rows above the kernel's limit {MAX_COHORT}")
+    if not 1 <= top_k <= nc:
+        raise ValueError(f"cohort_stats: top_k = {top_k} outside [1, Nc = {nc}]")
+    with torch.cuda.device(x.device):
+        out = torch.empty((2, n), dtype=torch.float32, device=x.device)
+        call("sv_cohort_topk_stats", ptr(x), x.stride(0), n, ptr(cohort), cohort.stride(0), nc, x.shape[1], top_k,
+             ptr(out[0]), ptr(out[1]), int(grid), stream_of(x))
+    return out[0], out[1]
+
+
+def cohort_models(d, speaker_off):
+    """The usual cohort, one row per speaker: the renormalised mean of each speaker's unit d-vectors
+    (d [U, proj], speaker s owns rows speaker_off[s] : speaker_off[s + 1]; sv_dvec_align)."""
+    from .ops import dvec_align
+    off = torch.from_numpy(np.asarray(speaker_off, dtype=np.int32)).to(d.device)
+    with torch.cuda.device(d.device):
+        return _unit_rows(dvec_align(d.contiguous(), off))
+
+
+def as_norm(x, cohort, top_k, std_floor=1e-5):
+    """(mu, inv) of one trial side for trial_histograms' norm_a / norm_b: cohort_stats' mean, and
+    inv = 1 / max(std, std_floor)."""
+    mu, sd = cohort_stats(x, cohort, top_k)
+    return mu, 1.0 / torch.clamp(sd, min=float(std_floor))
+
+
+def norm_range(norm_a, norm_b=None, s_max=1.0):
+    """(lo, hi): a range [lo, hi) that contains z = 0.5 ((s - mu_a[i]) inv_a[i] + (s - mu_b[j]) inv_b[j])
+    for every pair (i, j) and every |s| <= s_max, given inv > 0 (norm_b=None: norm_a on both sides).  z
+    rises with s, so each side's extremes are taken at s = -s_max and s = +s_max; the sum of the sides'
+    extremes, in fp64, is widened by 2^-20 of its size for the kernel's five fp32 roundings (2^-22
+    would do) and rounded outwards to fp32.  It is where the first histogram pass of normalised scores
+    looks, as [-1, 1) is for cosines; typically tens of units wide."""
+    lo = hi = 0.0
+    for mu, inv in (norm_a, norm_a if norm_b is None else norm_b):
+        mu, inv = mu.double(), inv.double()
+        lo += 0.5 * float(((-s_max - mu) * inv).min())
+        hi += 0.5 * float(((s_max - mu) * inv).max())
+    pad = 2.0 ** -20 * max(abs(lo), abs(hi), 1.0)
+    return (float(np.nextafter(np.float32(lo - pad), np.float32(-np.inf))),
+            float(np.nextafter(np.float32(hi + pad), np.float32(np.inf))))
 
 
 # ----------------------------------------------------------------------------- ROC arithmetic (host)
@@ -193,28 +284,43 @@ def _zoom(h):
     return (float(lo), float(hi)) if hi > lo and (hi - lo) / h.bins > 0 else None
 
 
-def _passes(a, lab_a, b, lab_b, bins, passes):
-    """The histograms of the passes that ran: the first over [-1, 1), each further one over _zoom of
-    the one before, everything outside carried by its under- and overflow slots."""
+def _passes(a, lab_a, b, lab_b, bins, passes, norm_a=None, norm_b=None, lo=None, hi=None):
+    """The histograms of the passes that ran: the first over [lo, hi) -- by default [-1, 1), with
+    norm_a norm_range's -- each further one over _zoom of the one before, everything outside carried
+    by its under- and overflow slots.  passes=None: 2, with norm_a 3."""
+    if passes is None:
+        passes = 2 if norm_a is None else 3
     if passes < 1:
         raise ValueError("passes must be >= 1")
-    hs = [trial_histograms(a, lab_a, b, lab_b, bins=bins, lo=-1.0, hi=1.0)]
+    if (lo is None) != (hi is None):
+        raise ValueError("give lo and hi together, or neither")
+    if lo is None:
+        lo, hi = (-1.0, 1.0) if norm_a is None else norm_range(norm_a, norm_b)
+    kw = {} if norm_a is None else {"norm_a": norm_a, "norm_b": norm_b}
+    hs = [trial_histograms(a, lab_a, b, lab_b, bins=bins, lo=lo, hi=hi, **kw)]
     while len(hs) < passes:
         z = _zoom(hs[-1])
         if z is None:
             break
-        hs.append(trial_histograms(a, lab_a, b, lab_b, bins=bins, lo=z[0], hi=z[1]))
+        hs.append(trial_histograms(a, lab_a, b, lab_b, bins=bins, lo=z[0], hi=z[1], **kw))
     return hs
 
 
-def corpus_eer(a, lab_a, b=None, lab_b=None, bins=4096, passes=2):
+def corpus_eer(a, lab_a, b=None, lab_b=None, bins=4096, passes=None, norm_a=None, norm_b=None, lo=None, hi=None):
     """(eer, threshold, far, frr, eer_lo, eer_hi, resolution) of all trials of unit rows a (and b):
     pass 1 bins the cosines over [-1, 1); each further pass reruns the kernel with [lo, hi) set to the
     two bins around the crossing of the pass before (after two passes of 4096 bins a range about
     2.4e-7 wide), the scores outside it carried by the under- and overflow slots, whose counts
     enter FAR and FRR exactly.  The tuple is eer() of the last pass plus its bin width.  A crossing
-    outside [-1, 1) ends the passes early."""
-    h = _passes(a, lab_a, b, lab_b, bins, passes)[-1]
+    outside the first range ends the passes early.
+
+    norm_a (norm_b) = (mu, inv): the trials of the AS-normalised score z (trial_histograms).  Pass 1
+    then covers norm_range(norm_a, norm_b) -- or the given [lo, hi) -- a range W of tens of units.
+
+    passes=None is 2 passes for cosines and 3 for normalised scores: bins of W / 4096, then W / 2^23,
+    then W / 2^34 (2.3e-9 at W = 40, below the spacing of fp32 values of z wherever |z| > 0.02: the
+    last pass separates every pair of distinct normalised scores there)."""
+    h = _passes(a, lab_a, b, lab_b, bins, passes, norm_a, norm_b, lo, hi)[-1]
     return eer(h) + (h.width,)
 
 
@@ -334,7 +440,8 @@ def trials_of(d, speaker_off, enroll=None):
             torch.arange(S, dtype=torch.int32, device=dev))
 
 
-def evaluate(net, corpus, enroll=None, T=TRAIN_FRAMES, precision="f32", bins=4096, passes=2, p_target=0.01):
+def evaluate(net, corpus, enroll=None, T=TRAIN_FRAMES, precision="f32", bins=4096, passes=None, p_target=0.01,
+             cohort=None, top_k=300, std_floor=1e-5):
     """Verification quality of ``net`` on a data_load.DeviceCorpus: a dict with eer, threshold, eer_lo,
     eer_hi (corpus_eer on the trials), min_dcf (of the first pass, all of [-1, 1), at p_target with unit
     costs), n_target and n_nontarget.  The d-vectors are corpus_dvectors(net, corpus, T, precision=...).
@@ -346,9 +453,32 @@ def evaluate(net, corpus, enroll=None, T=TRAIN_FRAMES, precision="f32", bins=409
 
     Unlike test(), the own-speaker score uses the enrolment model as it stands: there is no
     leave-one-out centroid, no batches of hp.test.N speakers and no 50-point threshold grid, so the
-    two figures are not comparable."""
+    two figures are not comparable.
+
+    cohort: adaptive symmetric score normalisation (AS-norm).  Either a float32 [Nc, proj] device
+    tensor of unit rows, or a DeviceCorpus, which is embedded with corpus_dvectors (same T and
+    precision) and reduced to one model per speaker with cohort_models.  Both sides of every trial --
+    the utterances, or with enroll=k the tests and the speaker models -- get the mean and std of their
+    top_k cohort scores (cohort_stats), inv = 1 / max(std, std_floor), and the trials are those of
+    z = 0.5 ((s - mu_e) inv_e + (s - mu_t) inv_t): three zoom passes by default, the first over
+    norm_range.  threshold and min_dcf are then on the scale of z, and the dict also carries
+    score_norm = "as-norm", top_k, n_cohort and range, the first pass's (lo, hi).  ValueError for
+    top_k > Nc.  The cohort must not contain the evaluated speakers: their own utterances among the
+    top scores shrink the normalised target scores.  That is the caller's responsibility; nothing
+    here can check it.  Without cohort the dict is the un-normalised one, unchanged."""
     d = corpus_dvectors(net, corpus, T=T, precision=precision)
-    hs = _passes(*trials_of(d, corpus.speaker_off, enroll), bins, passes)
+    a, lab_a, b, lab_b = trials_of(d, corpus.speaker_off, enroll)
+    if cohort is None:
+        hs = _passes(a, lab_a, b, lab_b, bins, passes)
+        extra = {}
+    else:
+        if not torch.is_tensor(cohort):
+            cohort = cohort_models(corpus_dvectors(net, cohort, T=T, precision=precision), cohort.speaker_off)
+        norm_a = as_norm(a, cohort, top_k, std_floor)
+        norm_b = None if b is None else as_norm(b, cohort, top_k, std_floor)
+        hs = _passes(a, lab_a, b, lab_b, bins, passes, norm_a, norm_b)
+        extra = {"score_norm": "as-norm", "top_k": int(top_k), "n_cohort": int(cohort.shape[0]),
+                 "range": (hs[0].lo, hs[0].hi)}
     e, thr, _, _, e_lo, e_hi = eer(hs[-1])
     return {"eer": e, "threshold": thr, "eer_lo": e_lo, "eer_hi": e_hi, "min_dcf": min_dcf(hs[0], p_target),
-            "n_target": hs[0].n_target, "n_nontarget": hs[0].n_nontarget}
+            "n_target": hs[0].n_target, "n_nontarget": hs[0].n_nontarget, **extra}
