@@ -653,6 +653,72 @@ int sv_trial_hist_norm(const float* A, long lda, const int* lab_a, int Na, const
                        const float* inv_a, const float* mu_b, const float* inv_b, unsigned long long* hist, int grid,
                        hipStream_t stream);
 
+/* ---- spectral diarization (added under v12; additive): the device steps of Wang et al., "Speaker
+ * Diarization with LSTM" (arXiv 1710.10468) on a ragged batch of F files of unit d-vectors
+ * (diarization.py has the pipeline; sv_diar.hip the kernel plans).
+ *   Layout: file f owns the rows row_off[f] .. row_off[f + 1] (device int32 [F + 1], n_f rows) of every
+ *   [sum n][.] array, and an n_f x n_f fp32 matrix with leading dimension ld_f = (n_f + 3) & ~3 at
+ *   element mat_off[f] (device 64-bit [F], multiples of 4) of every packed matrix buffer.  Every
+ *   function that writes a matrix writes zeros into its columns n_f .. ld_f - 1, so the matrix is a
+ *   k-contiguous sv_gemm_f32 operand with K = ld_f.  n_max: an upper bound of the n_f, given by the
+ *   host; it sizes the grids, and rows past it are not processed.
+ *   No function waits between workgroups; every stage boundary is a launch boundary on `stream`.
+ *
+ * sv_diar_crop_blur: A_ii := max_{j != i} A_ij, then B = W A W^T with W_ij = g(|i - j|) / c_i for
+ *   |i - j| <= r, c_i the sum of row i's in-range taps (edges renormalise, nothing is padded).
+ *   taps: HOST pointer to the r + 1 values g(0) .. g(r); r = 0 with g(0) = 1 is W = I.  A is overwritten
+ *   (it holds the row pass's result).  |B - exact| <= ((2 r + 1)^2 + 8) 2^-24 max|A|.
+ * sv_diar_row_select: tau[row_off[f] + i] = the element of ascending rank q[f] (0-based, device int32
+ *   [F], clamped to [0, n_f - 1]) of row i of B: an exact radix select on the order-preserving key of
+ *   sv_cohort_topk_stats, ties included; a NaN sorts above +inf.
+ * sv_diar_thresh_sym: Y_ij = fmaxf(T_ij, T_ji) with T_ij = B_ij >= tau_i ? B_ij : mult * B_ij (one fp32
+ *   multiplication).  Y must not be B.
+ * sv_diar_row_norm: d_i = max_j Z_ij (exact), r_i = 1 / sqrt(d_i) in fp64, or 0 if d_i <= 0, and
+ *   S_ij = Z_ij (r_i r_j), the product formed in fp64 and rounded once: |S - exact| <= 2^-24 |S|, S is
+ *   symmetric bit for bit where Z is, and a row with d_i <= 0 gives a zero row and column.  r: [sum n]
+ *   doubles (output).  S may be Z.
+ * sv_diar_spmm: P = S (W T) for W, P [sum n][SV_DIAR_M] fp32 and T [F][16][16] fp64 row-major: the
+ *   operand Q = W T is formed on the fly (fp64 products, rounded to fp32), the products S Q on the
+ *   exact fp32 MFMA in a fixed order.  S is read once.  P must not be W.
+ * sv_diar_gram: G[f] = X_f^T Y_f, [F][16][16] fp64, from fp32 X, Y [sum n][16]: fp64 products and sums,
+ *   256-row blocks and then the blocks in ascending order through `workspace` (sv_diar_workspace bytes;
+ *   no floating-point atomics: the same input gives the same bits).
+ * sv_diar_rmul: Y = X T (fp64 products, rounded once).  With P != NULL also res2[f][j] = the squared
+ *   norm of column j of P_f T_f - Y_f diag(lam[f]) ([F][16] fp64 each), summed in the same two levels;
+ *   P NULL: lam, res2 and workspace are not used.  Y must be neither X nor P.
+ * sv_diar_kmeans: Lloyd's algorithm on the rows of E [sum n][16] (unused columns zero), one workgroup
+ *   per file, k[f] (device int32, clamped to [1, min(16, n_f)]) centres.  Start: row 0, then
+ *   repeatedly the row whose fp32 squared distance to the nearest chosen centre is largest (ties: the
+ *   lowest row).  A pass assigns every row to its nearest centre (ties: the lowest centre); if a
+ *   label changed, every non-empty cluster's centre becomes the mean of its rows (fp64 sum in row
+ *   order, rounded once; an empty cluster keeps its centre) and the next pass runs, up to max_iter
+ *   passes.  labels [sum n] int32 (centre indices), iters [F] the passes that ran.
+ * SV_EARG: a null pointer (P of sv_diar_rmul may be NULL); F or n_max < 1; r < 0; max_iter < 1; an
+ * output that must not alias an input and does.  SV_EALIGN: a matrix, W, P, X / Y of sv_diar_rmul or E
+ * off a 16-byte boundary; a 64-bit table or fp64 array off an 8-byte, anything else off a 4-byte one.
+ * SV_ESHAPE: n_max > SV_DIAR_MAX_N (a row is staged in LDS); F > 65 535; r > SV_DIAR_MAX_R.  Checked in
+ * that order, all before any launch. */
+#define SV_DIAR_M 16
+#define SV_DIAR_MAX_N 8192
+#define SV_DIAR_MAX_R 8
+int sv_diar_crop_blur(float* A, float* B, const int* row_off, const long* mat_off, int F, int n_max,
+                      const float* taps, int r, hipStream_t stream);
+int sv_diar_row_select(const float* B, const int* row_off, const long* mat_off, int F, int n_max, const int* q,
+                       float* tau, hipStream_t stream);
+int sv_diar_thresh_sym(const float* B, const float* tau, float mult, float* Y, const int* row_off, const long* mat_off,
+                       int F, int n_max, hipStream_t stream);
+int sv_diar_row_norm(const float* Z, float* S, float* d, double* r, const int* row_off, const long* mat_off, int F,
+                     int n_max, hipStream_t stream);
+int sv_diar_spmm(const float* S, const float* W, const double* T, float* P, const int* row_off, const long* mat_off,
+                 int F, int n_max, hipStream_t stream);
+size_t sv_diar_workspace(int F, int n_max);
+int sv_diar_gram(const float* X, const float* Y, double* G, double* workspace, const int* row_off, int F, int n_max,
+                 hipStream_t stream);
+int sv_diar_rmul(const float* X, const double* T, float* Y, const float* P, const double* lam, double* res2,
+                 double* workspace, const int* row_off, int F, int n_max, hipStream_t stream);
+int sv_diar_kmeans(const float* E, const int* row_off, const int* k, int F, int max_iter, int* labels, int* iters,
+                   hipStream_t stream);
+
 /* ---- clip_grad_norm_ + SGD step over one flat parameter group (train_speech_embedder.py:63-65)
  * p -= lr * min(1, max_norm / (|g|_2 + 1e-6)) * g; write_grad=1 also scales g in place.
  * sync (may be NULL): a persistent-recurrence sync block; if its status is set the step is

@@ -165,6 +165,16 @@ SIGNATURES = {
     "sv_cohort_topk_stats": (_c_int, [_P, _c_long, _c_int, _P, _c_long, _c_int, _c_int, _c_int, _P, _P, _c_int, _P]),
     "sv_trial_hist_norm": (_c_int, [_P, _c_long, _P, _c_int, _P, _c_long, _P, _c_int, _c_int, _c_int, _c_float,
                                     _c_float, _c_int, _P, _P, _P, _P, _P, _c_int, _P]),
+    # spectral diarization (diarization.py): tables are (row_off, mat_off, F, n_max)
+    "sv_diar_crop_blur": (_c_int, [_P, _P, _P, _P, _c_int, _c_int, _P, _c_int, _P]),
+    "sv_diar_row_select": (_c_int, [_P, _P, _P, _c_int, _c_int, _P, _P, _P]),
+    "sv_diar_thresh_sym": (_c_int, [_P, _P, _c_float, _P, _P, _P, _c_int, _c_int, _P]),
+    "sv_diar_row_norm": (_c_int, [_P, _P, _P, _P, _P, _P, _c_int, _c_int, _P]),
+    "sv_diar_spmm": (_c_int, [_P, _P, _P, _P, _P, _P, _c_int, _c_int, _P]),
+    "sv_diar_workspace": (_c_size_t, [_c_int, _c_int]),
+    "sv_diar_gram": (_c_int, [_P, _P, _P, _P, _P, _c_int, _c_int, _P]),
+    "sv_diar_rmul": (_c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _c_int, _c_int, _P]),
+    "sv_diar_kmeans": (_c_int, [_P, _P, _P, _c_int, _c_int, _P, _P, _P]),
     "sv_clip_sgd_workspace": (_c_size_t, []),
     "sv_clip_sgd_step": (_c_int, [_P, _P, _c_long, _c_float, _c_float, _c_int, _P, _P, _P, _P]),
     "sv_clip_sgd_step2": (_c_int, [_P, _P, _c_long, _c_float, _P, _P, _c_long, _c_float, _c_float, _c_int, _P, _P, _P,

@@ -373,7 +373,7 @@ def _batches(sizes, max_samples):
 
 
 @torch.no_grad()
-def embed_files(net, files, precision="bf16", path=None, max_samples=2 ** 27, **kw):
+def embed_files(net, files, precision="bf16", path=None, max_samples=2 ** 27, on_device=False, **kw):
     """Aligned d-vectors of many files: `files` is a list of (waveform, ranges), a decoded mono
     waveform at hp.data.sr and its voiced sample ranges [(a, b)] (voiced_ranges); returns one
     float64 [n_aligned_i, proj] array per file, in order -- per file what
@@ -389,7 +389,9 @@ def embed_files(net, files, precision="bf16", path=None, max_samples=2 ** 27, **
     (fp32, small bf16 batches, path == "persist"): the windows of one chunk at a time gathered on the
     device from the same table (windows_from_logmel's gather) and embed_windows(**kw) on them, so
     the window tensor stays bounded by the chunk (kw's `batch`, else embed_windows' default).
-    Raises PersistentRecurrenceError like embed_windows."""
+    on_device=True skips the copy out: a file with d-vectors then gets a float64 device tensor (a view
+    of its batch's sv_dvec_align output) instead of an array, for consumers on the GPU
+    (diarization.diarize).  Raises PersistentRecurrenceError like embed_windows."""
     from .features import _config, logmel_ranges
     _check_path(precision, path)
     _, _, _, hop_n, nmels = _config(None, None, None, None, None)
@@ -425,7 +427,9 @@ def embed_files(net, files, precision="bf16", path=None, max_samples=2 ** 27, **
                 emb = [embed_windows(net, out[win_start[i:i + chunk].long()[:, None] + steps[None, :]], precision=precision,
                                      path=path, **kw) for i in range(0, S, chunk)]
             emb = emb[0] if len(emb) == 1 else torch.cat(emb)
-            aligned = dvec_align(emb, part_off).cpu().numpy()
+            aligned = dvec_align(emb, part_off)
+            if not on_device:
+                aligned = aligned.cpu().numpy()
         pos = 0
         for i, n in zip(ids, n_parts):
             results[i] = aligned[pos:pos + n]

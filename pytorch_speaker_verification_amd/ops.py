@@ -797,3 +797,15 @@ def gemm_f32(A, B, a_kcontig=True, b_kcontig=True, bias=None, products="mfma_f32
     call("sv_gemm_f32", int(a_kcontig), int(b_kcontig), M, N, K, ptr(A), A.shape[1], ptr(B), B.shape[1], ptr(C), N,
          ptr(bias), None, 0.0, ptr(ws), _products(products), stream_of(A))
     return C
+
+
+def gemm_f32_nt_into(A, lda, B, ldb, C, ldc, M, N, K):
+    """C[m * ldc + n] = sum_k A[m * lda + k] B[n * ldb + k] through sv_gemm_f32 (exact fp32 MFMA products):
+    A, B and C are 1-D fp32 device views that start at the operands, so that the callers' packed
+    buffers (diarization.py: one matrix per file at its own offset and leading dimension) need no
+    copies.  K, lda and ldb multiples of 4, A and B on 16-byte boundaries (the kernel's own checks)."""
+    require_device(A, B, C)
+    if A.numel() < (M - 1) * lda + K or B.numel() < (N - 1) * ldb + K or C.numel() < (M - 1) * ldc + N:
+        raise ValueError("gemm_f32_nt_into: an operand view is shorter than its matrix")
+    ws = _ws(lib().sv_gemm_f32_workspace(M, N, K), A.device)
+    call("sv_gemm_f32", 1, 1, M, N, K, ptr(A), lda, ptr(B), ldb, ptr(C), ldc, None, None, 0.0, ptr(ws), 0, stream_of(A))
