@@ -1,5 +1,5 @@
-// bf16 GEMM building blocks shared by the step kernels (sv_bf16.hip) and the persistent
-// recurrences (sv_persist.hip): bf16 storage type, k-major LDS tile staging, the
+// bf16 GEMM building blocks shared by the GEMMs (sv_gemm_bf16.hip), the step kernels (sv_bf16.hip)
+// and the persistent recurrences (sv_persist.hip): bf16 storage type, k-major LDS tile staging, the
 // v_mfma_f32_32x32x16_bf16 k-tile, and the main loops over them.
 #pragma once
 #include "sv_common.h"

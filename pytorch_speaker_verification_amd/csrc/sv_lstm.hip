@@ -18,6 +18,7 @@
 #include <algorithm>
 #include "sv_common.h"
 #include "sv_gemm.h"
+#include "sv_lstm_stack.h"
 #include "../../include/sv_ge2e.h"
 
 // [B, T, F] (batch_first) -> [T, B, F]
@@ -415,39 +416,8 @@ BwdWs carve_bwd(float* base, int T, int B, int F, int H) {
 // GEMM's stream-K scratch (gf_sk_bytes)
 size_t ws_per(int T, int B, int F, int H) { return al256(carve_bwd(nullptr, T, B, std::max(F, H), H).total); }
 size_t ws_handoff(int T, int B, int H) { return H == 768 ? al256(sv_persist_f32_bwd_scratch(T, B, H)) : 0; }
-int record(hipEvent_t e, hipStream_t s) { return (int)hipEventRecord(e, s); }
-int stream_wait(hipStream_t s, hipEvent_t e) { return (int)hipStreamWaitEvent(s, e, 0); }
-
-// The validated shape and scheduling arguments of sv_lstm_stack_fwd / sv_lstm_stack_bwd (named as
-// in their signatures) and what both schedules derive from them.  Fwd and Bwd add a direction's
-// arrays and one layer's sequences, each written once and run on the stream it is given; the
-// single-layer entry points run those on a stack of one layer.
-struct Stack {
-  int L, T, B, F, H, chunk;
-  hipStream_t main;
-  const hipStream_t* side;
-  hipEvent_t *ev, *probe;
-  int products, schedule;
-  unsigned* sync;
-  // derived: chunks; B rounded up to 4, the column block of hT [H, (T+1) Bp] and dgT [4H, T Bp]
-  int nch = (T + chunk - 1) / chunk, Bp = (B + 3) & ~3, TBp = T * Bp;
-  long BH = (long)B * H, BG = 4L * B * H, ldhT = (long)(T + 1) * Bp;
-  int Fl(int l) const { return l == 0 ? F : H; }
-  int t0(int c) const { return c * chunk; }
-  int t1(int c) const { return std::min(T, (c + 1) * chunk); }
-  // ev: chunk c of layer l done | the forward's fork from main | backward layer l done | the
-  // backward's fork (forward L nch + 1 events, backward L nch + L + 1)
-  hipEvent_t chunk_done(int l, int c) const { return ev[l * nch + c]; }
-  hipEvent_t fwd_start() const { return ev[L * nch]; }
-  hipEvent_t layer_done(int l) const { return ev[L * nch + l]; }
-  hipEvent_t bwd_start() const { return ev[L * nch + L]; }
-  // probe (or NULL) in pairs: persistent, 2 L events, pair l around layer l's launch; per-step
-  // backward, 2 L nch events, pair (l, c) around one K3 launch of layer l's chunk c
-  hipEvent_t* layer_probe(int l) const { return probe ? probe + 2 * l : nullptr; }
-  hipEvent_t* chunk_probe(int l, int c) const { return probe ? probe + 2 * (l * nch + c) : nullptr; }
-};
-
-struct Fwd : Stack {
+// One layer's sequences on the shared stack frame (sv_lstm_stack.h), batch padded to 4
+struct Fwd : Stack<4> {
   const float* x_tm;
   const float *const *w_ih, *const *w_hh, *const *b_ih, *const *b_hh;
   float *const *gates, *const *c_tm, *const *h_tm, *const *hT;
@@ -476,7 +446,7 @@ struct Fwd : Stack {
   }
 };
 
-struct Bwd : Stack {
+struct Bwd : Stack<4> {
   const float* const* xT;
   const long* ld_xT;
   const float *const *w_ih, *const *w_hh, *const *gates, *const *c_tm, *const *hT;
@@ -615,25 +585,6 @@ static int fwd_persist(const Fwd& a) {
   return SV_OK;
 }
 
-static int fwd_per_step(const Fwd& a) {
-  int rc = record(a.fwd_start(), a.main);
-  for (int l = 0; l < a.L && !rc; ++l)
-    if (!(rc = stream_wait(a.side[l], a.fwd_start()))) rc = a.reset(l, a.side[l]);
-  if (rc) return rc;
-  // wavefront issue order: chunk c of layer l after chunk c of layer l-1 on the host too
-  for (int d = 0; d < a.nch + a.L - 1; ++d)
-    for (int l = 0; l < a.L; ++l) {
-      const int c = d - l;
-      if (c < 0 || c >= a.nch) continue;
-      hipStream_t s = a.side[l];
-      if (l > 0 && (rc = stream_wait(s, a.chunk_done(l - 1, c)))) return rc;
-      if ((rc = a.k1(l, a.t0(c), a.t1(c), s)) || (rc = a.steps(l, a.t0(c), a.t1(c), s))) return rc;
-      if ((rc = record(a.chunk_done(l, c), s))) return rc;
-    }
-  for (int l = 0; l < a.L && !rc; ++l) rc = stream_wait(a.main, a.chunk_done(l, a.nch - 1));
-  return rc;
-}
-
 extern "C" int sv_lstm_stack_fwd(int L, int T, int B, int F, int H, const float* x_tm, const float* const* w_ih,
                                  const float* const* w_hh, const float* const* b_ih, const float* const* b_hh,
                                  float* const* gates, float* const* c_tm, float* const* h_tm, float* const* hT,
@@ -646,7 +597,7 @@ extern "C" int sv_lstm_stack_fwd(int L, int T, int B, int F, int H, const float*
   const Fwd a{{L, T, B, F, H, chunk, main, side, ev, probe, products, schedule, sync},
               x_tm, w_ih, w_hh, b_ih, b_hh, gates, c_tm, h_tm, hT};
   if (f32_persist(schedule, B, H, main)) return sync ? fwd_persist(a) : SV_EARG;
-  return fwd_per_step(a);
+  return stack_fwd_per_step(a);
 }
 
 // Stack backward, top layer first in issue order.  Per-step: layer l's timesteps in reverse chunks
@@ -693,25 +644,6 @@ static int bwd_persist(const Bwd& a) {
   return events ? record(a.layer_done(0), a.main) : SV_OK;
 }
 
-static int bwd_per_step(const Bwd& a) {
-  int rc = record(a.bwd_start(), a.main);
-  for (int l = a.L - 1; l >= 0 && !rc; --l) {
-    hipStream_t s = a.side[l];
-    const BwdWs ws = a.region(l);
-    if ((rc = stream_wait(s, a.bwd_start())) || (rc = a.prepare(l, ws, l > 0, true, s))) return rc;
-    for (int c = a.nch - 1; c >= 0; --c) {
-      if (l < a.L - 1 && (rc = stream_wait(s, a.chunk_done(l + 1, c)))) return rc;
-      rc = a.steps(l, ws, a.t0(c), a.t1(c), s, a.chunk_probe(l, c));
-      if (!rc && l > 0) rc = a.dx_gemm(l, ws, a.t0(c), a.t1(c), s);  // dh_up of layer l-1 for this chunk
-      if (rc || (rc = record(a.chunk_done(l, c), s))) return rc;
-    }
-    // whole-T weight gradients and bias row sums behind the recurrence, on its stream
-    if (!(rc = a.grads(l, ws, true, s))) rc = record(a.layer_done(l), s);
-  }
-  for (int l = 0; l < a.L && !rc; ++l) rc = stream_wait(a.main, a.layer_done(l));
-  return rc;
-}
-
 extern "C" int sv_lstm_stack_bwd(int L, int T, int B, int F, int H, const float* const* xT, const long* ld_xT,
                                  const float* const* w_ih, const float* const* w_hh, const float* const* gates,
                                  const float* const* c_tm, const float* const* hT, const float* dh_last,
@@ -730,5 +662,5 @@ extern "C" int sv_lstm_stack_bwd(int L, int T, int B, int F, int H, const float*
               gates, c_tm, hT, dh_last, 0, dgates, dgT, dx, dw_ih, dw_hh, db_ih, db_hh, (char*)workspace, kstamp,
               ws_per(T, B, F, H)};
   if (f32_persist(schedule, B, H, main)) return sync ? bwd_persist(a) : SV_EARG;
-  return bwd_per_step(a);
+  return stack_bwd_per_step(a);
 }

@@ -4,7 +4,7 @@
 // misses per bf16 step launch ~ the per-XCD W_hh + h footprint).  Here each workgroup keeps the
 // same (row block, unit block) tile for the whole sequence: its W_hh slice stays in the XCD's
 // L2, its cell state stays in registers, and only h_{t-1} crosses workgroups.  Selected by
-// (see persist_fwd() in sv_bf16.hip for when the stack forward uses it).
+// (see fwd_persist() and sched_persist() in sv_bf16.hip for when the stack forward uses it).
 //
 // Hand-off of h between timesteps (MI355X_MICROARCH.md, inter-workgroup visibility, hand-off
 // table row 1): every store of the handed-off bytes (h_bf[t+1], 4-B packed pairs) is an `sc1`

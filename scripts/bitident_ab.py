@@ -1,11 +1,13 @@
 """Bit-identity check of an A/B build against the product library, with fixed inputs; --out saves
 every output tensor (torch.save of this script's own tensors), --compare A B reports the tensors
-that differ.  Default: the bf16 stack forward + backward at a rank shape (c4: B = 80, T = 160).
+that differ.  Default: the bf16 stack forward + backward at a rank shape (c4: B = 80, T = 160),
+under --schedule (auto | per_step | per_layer | persist, passed to both), so the case can be saved
+once per schedule.
 --ge2e: the GE2E loss kernels on every case of tests/ge2e_cases.py and tests/contrast_cases.py, both
 losses: the fused step, the split forward and backward (with GLOSS on its case), the sharded
 three-call forms (fused and split) on the tables' shard lists, and the stand-alone helper ops with
 their backward passes; saves loss, per, dE, dwdb and every shard's reduce buffer.
-Usage: python scripts/bitident_ab.py [--ge2e] [--lib L] --out f.pt ; python scripts/bitident_ab.py --compare a.pt b.pt"""
+Usage: python scripts/bitident_ab.py [--ge2e | --schedule S] [--lib L] --out f.pt ; python scripts/bitident_ab.py --compare a.pt b.pt"""
 import argparse
 import os
 import sys
@@ -21,6 +23,7 @@ ap.add_argument("--B", type=int, default=80)
 ap.add_argument("--T", type=int, default=160)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--ge2e", action="store_true")
+ap.add_argument("--schedule", default="auto", choices=["auto", "per_step", "per_layer", "persist"])
 args = ap.parse_args()
 if args.compare:
     a, b = (torch.load(f, weights_only=True) for f in args.compare)
@@ -124,9 +127,9 @@ wp, bp = net.projection.weight, net.projection.bias
 ps = PersistStatus(dev)
 out = {}
 for r in range(args.reps):  # repeated: every launch must give the same bits
-    emb, st = ops.embedder_forward_bf16(x, layers, wp, bp, save=True, status=ps)
+    emb, st = ops.embedder_forward_bf16(x, layers, wp, bp, save=True, status=ps, schedule=args.schedule)
     demb = torch.randn(emb.shape, generator=torch.Generator(device=dev).manual_seed(7), device=dev) * 0.1
-    grads = ops.embedder_backward_bf16(st, demb, layers, wp, status=ps)
+    grads = ops.embedder_backward_bf16(st, demb, layers, wp, status=ps, schedule=args.schedule)
     torch.cuda.synchronize()
     flat = {"emb": emb}
     for i, g in enumerate(grads if isinstance(grads, (list, tuple)) else [grads]):

@@ -24,6 +24,7 @@ Rounding points (read in the kernels; all match include/sv_ge2e.h's bf16 variant
   So every form computes q(XP) + h q(W_hh)^T; where XP cannot be read back the verifier assumes
   XP = q(xp64) and gives the cells with a tie-near x-projection element the loose bound.
 """
+import ctypes
 import functools
 
 import numpy as np
@@ -356,3 +357,56 @@ def test_stack_bf16_h768(B, T, schedule):
         fused = (0,)
     _check_stack(f"h768.{schedule}.B{B}T{T}", (B, F, H, L, T, bf16_cases.P_768), schedule, False, fused=fused,
                  device=DEV, slots="last")
+
+
+# ------------------------------------------------------------------------- d. a stack of one layer
+def _bits(t):
+    return t.view(torch.int16 if t.dtype == BF else torch.int32)
+
+
+# the smallest (B, F, H) case with B % 8 != 0 (Bp padding: hT and dgT zeroed), and the next one, whose
+# T = 3 also runs a K1 of several steps and the backward's dcf ping-pong
+@pytest.mark.parametrize("B,F,H,T", sorted(c for c in bf16_cases.LAYER_CASES if c[0] % 8)[:2])
+def test_stack_of_one_layer_is_the_layer_bf16(B, F, H, T):
+    """The single-layer entry points and the per-step stack run one set of host pieces (the BFwd /
+    BBwd sequences of sv_bf16.hip): under per_step, sv_lstm_stack_fwd_bf16 with L = 1 gives gates, c,
+    h, h_bf and hT bit-identical to sv_lstm_layer_fwd_bf16, and sv_lstm_stack_bwd_bf16 with L = 1
+    (its wt filled by sv_lstm_weights_bf16, SV_SCHED_WT_READY) gives dg, dgT, dW_ih, dW_hh and db
+    bit-identical to sv_lstm_layer_bwd_bf16 without dx_tm, both from the same forward buffers."""
+    from pytorch_speaker_verification_amd import ops
+    lib_ = _lib()
+    c = _layer_fwd(B, F, H, T)
+    wd, d, st = c["wd"], c["dev"], c["st"]
+    Bp, dev, sched = st["Bp"], torch.device(DEV, 0), lib_.schedule_flags("per_step")
+    one = lambda t: ops._parr([t])  # noqa: E731
+    x_bf = st["x_bf"].to(DEV)
+    o = dict(gates=_guarded(T * B, 4 * H, BF), c_tm=_guarded(T * B, H, F32), h_tm=_guarded((T + 1) * B, H, F32),
+             h_bf=_guarded((T + 1) * B, H, BF), hT=_guarded(H, (T + 1) * Bp, BF))
+    nch = (T + ops.PIPELINE_CHUNK - 1) // ops.PIPELINE_CHUNK
+    sp, ep, _ = ops._side(dev, "fwd", 1, nch + 1)
+    _call("sv_lstm_stack_fwd_bf16", 1, T, B, F, H, _ptr(x_bf), one(wd["w_ih_bf"]), one(wd["w_hh_bf"]),
+          one(wd["b_ih"]), one(wd["b_hh"]), one(o["gates"]), one(o["c_tm"]), one(o["h_tm"]), one(o["h_bf"]),
+          one(o["hT"]), ops.PIPELINE_CHUNK, _stream(), sp, ep, None, None, sched)
+    torch.cuda.synchronize()
+    for k, t in o.items():
+        _untouched(f"stack_of_one.{k}", t)
+        assert torch.equal(_bits(t[:-1].cpu()).reshape(-1), _bits(st[k][0]).reshape(-1)), f"forward {k} differs"
+
+    dh_last = torch.randn((B, H), generator=torch.Generator().manual_seed(B + F + H + T)).to(DEV)
+    ref = _layer_bwd(c, B, F, H, T, dh_last, 0, False, True)
+    wt = ops._ws(lib_.lib().sv_lstm_wt_bf16_size(1, F, H), dev)
+    w_bf = [torch.empty_like(wd["w_ih_bf"]), torch.empty_like(wd["w_hh_bf"])]
+    _call("sv_lstm_weights_bf16", 1, F, H, one(wd["w_ih"]), one(wd["w_hh"]), one(w_bf[0]), one(w_bf[1]), _ptr(wt),
+          _stream())
+    g = dict(dg=_guarded(T * B, 4 * H, BF), dgT=_guarded(4 * H, T * Bp, BF), dw_ih=_guarded(4 * H, F, F32),
+             dw_hh=_guarded(4 * H, H, F32), db_ih=_guarded(4 * H, 0, F32), db_hh=_guarded(4 * H, 0, F32))
+    ws = ops._ws(lib_.lib().sv_lstm_stack_bwd_bf16_workspace(1, T, B, F, H), dev)
+    sp, ep, _ = ops._side(dev, "bwd", 1, nch + 2)
+    _call("sv_lstm_stack_bwd_bf16", 1, T, B, F, H, one(d["xT"]), (ctypes.c_long * 1)(T * Bp), one(wd["w_ih"]),
+          one(wd["w_hh"]), one(d["gates"]), one(d["c_tm"]), one(d["hT"]), _ptr(dh_last), one(g["dg"]), one(g["dgT"]),
+          one(None), one(g["dw_ih"]), one(g["dw_hh"]), one(g["db_ih"]), one(g["db_hh"]), _ptr(ws), _ptr(wt),
+          ops.PIPELINE_CHUNK, _stream(), sp, ep, None, None, sched | lib_.SV_SCHED_WT_READY)
+    torch.cuda.synchronize()
+    for k, t in g.items():
+        _untouched(f"stack_of_one.{k}", t)
+        assert torch.equal(_bits(t), _bits(ref[k])), f"backward {k} differs"
