@@ -719,6 +719,35 @@ int sv_diar_rmul(const float* X, const double* T, float* Y, const float* P, cons
 int sv_diar_kmeans(const float* E, const int* row_off, const int* k, int F, int max_iter, int* labels, int* iters,
                    hipStream_t stream);
 
+/* ---- diarization scoring on a frame grid (added under v12; additive): segment tables to per-frame
+ * speaker bit masks, and the masks to the integers of the diarization error rate (diarization.der has
+ * the pipeline; sv_der.hip the kernel plans).  Every result is an integer and independent of the order
+ * in which workgroups run.
+ *   Grid: `step` samples per frame; frame i of a file has its centre at c_i = i * step + step / 2, and
+ *   a segment [s, e) in samples covers frame i iff s <= c_i < e.  File f owns the frames frame_off[f] ..
+ *   frame_off[f + 1] (device int32 [F + 1]) of every per-frame array; n_total is the length of those
+ *   arrays in frames (frame_off[F] for a packed batch), and nothing past it is read or written.
+ *
+ * sv_seg_raster: mask[frame_off[f] + i] |= seg_bits[k] for every frame i that row k = (seg_start[k],
+ *   seg_end[k], seg_bits[k], f = seg_file[k]) covers (device tables of n_seg rows; samples are int32),
+ *   clamped to the file's own frames.  A row with seg_file outside [0, F) or seg_end <= seg_start writes
+ *   nothing.  The caller zeroes mask (uint32 [n_total]).  One wave per row: the host keeps rows short
+ *   (diarization.split_rows); n_seg = 0 is no launch.
+ * sv_der_count: out [F][4 + 32 * 32] uint64, overwritten: per file, over its scored frames, with
+ *   Nr = popcount(ref), Nh = popcount(hyp): total = sum Nr, miss = sum max(0, Nr - Nh),
+ *   fa = sum max(0, Nh - Nr), both = sum min(Nr, Nh), then C[i][j] = the number of scored frames with
+ *   bit i of ref and bit j of hyp set.  A frame is scored iff noscore == 0, uem != 0 (uem may be NULL:
+ *   every frame) and, with skip_overlap != 0, Nr <= 1.  max_frames: an upper bound of the files' frame
+ *   counts, given by the host; it sizes the grid, and frames past it are not counted.
+ * SV_EARG: a null pointer (uem may be NULL); F < 1; step < 1; n_seg, max_frames or n_total < 0.
+ * SV_EALIGN: a per-frame array of sv_der_count off a 16-byte boundary, out off an 8-byte, anything else
+ * off a 4-byte one.  SV_ESHAPE: F > 65 535 (sv_der_count).  All before any launch. */
+int sv_seg_raster(const int* seg_start, const int* seg_end, const unsigned* seg_bits, const int* seg_file, int n_seg,
+                  const int* frame_off, int F, int step, int n_total, unsigned* mask, hipStream_t stream);
+int sv_der_count(const unsigned* ref, const unsigned* hyp, const unsigned* noscore, const unsigned* uem,
+                 const int* frame_off, int F, int max_frames, int n_total, int skip_overlap, unsigned long long* out,
+                 hipStream_t stream);
+
 /* ---- clip_grad_norm_ + SGD step over one flat parameter group (train_speech_embedder.py:63-65)
  * p -= lr * min(1, max_norm / (|g|_2 + 1e-6)) * g; write_grad=1 also scales g in place.
  * sync (may be NULL): a persistent-recurrence sync block; if its status is set the step is

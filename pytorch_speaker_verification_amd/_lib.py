@@ -175,6 +175,9 @@ SIGNATURES = {
     "sv_diar_gram": (_c_int, [_P, _P, _P, _P, _P, _c_int, _c_int, _P]),
     "sv_diar_rmul": (_c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _c_int, _c_int, _P]),
     "sv_diar_kmeans": (_c_int, [_P, _P, _P, _c_int, _c_int, _P, _P, _P]),
+    # diarization scoring (diarization.der): segment tables, (frame_off, F), step / max_frames, n_total
+    "sv_seg_raster": (_c_int, [_P, _P, _P, _P, _c_int, _P, _c_int, _c_int, _c_int, _P, _P]),
+    "sv_der_count": (_c_int, [_P, _P, _P, _P, _P, _c_int, _c_int, _c_int, _c_int, _P, _P]),
     "sv_clip_sgd_workspace": (_c_size_t, []),
     "sv_clip_sgd_step": (_c_int, [_P, _P, _c_long, _c_float, _c_float, _c_int, _P, _P, _P, _P]),
     "sv_clip_sgd_step2": (_c_int, [_P, _P, _c_long, _c_float, _P, _P, _c_long, _c_float, _c_float, _c_int, _P, _P, _P,

@@ -13,12 +13,18 @@ with LSTM" (arXiv 1710.10468), on ragged batches of files and on the GPU through
   spectral_embedding, kmeans
                      row-normalised leading eigenvectors; Lloyd's algorithm, one workgroup per file
   cluster, diarize   the whole chain on a list of d-vector sequences / of (waveform, ranges) files
+  segments, write_rttm, read_rttm
+                     labels to wall-clock time: the samples every aligned d-vector owns
+                     (dvector.aligned_spans) carry its label; RTTM out and in
+  raster, count, assignment, der, evaluate
+                     scoring: segment tables to per-frame speaker bit masks (sv_seg_raster), the
+                     masks to the integers of the diarization error rate for all files of a batch in
+                     one pass (sv_der_count), the optimal speaker mapping on the host
 
-The kernels are sv_diar_* (include/sv_ge2e.h has their contracts, csrc/sv_diar.hip their plans); the
-two n^3 products run on sv_gemm_f32.  What stays in torch is plumbing: the batched 16 x 16 fp64
-eigh of the subspace iteration, the row normalisation of the embedding and the eigengap on the host.
-There is no CPU path.  The result is a label per aligned d-vector: mapping labels back to wall-clock
-time needs the times of the partitions, which the export this builds on does not carry either.
+The kernels are sv_diar_* and sv_seg_raster / sv_der_count (include/sv_ge2e.h has their contracts,
+csrc/sv_diar.hip and csrc/sv_der.hip their plans); the two n^3 products run on sv_gemm_f32.  What
+stays in torch is plumbing: the batched 16 x 16 fp64 eigh of the subspace iteration, the row
+normalisation of the embedding and the eigengap on the host.  There is no CPU path.
 """
 from __future__ import annotations
 
@@ -26,6 +32,7 @@ import numpy as np
 import torch
 
 from ._lib import call, lib, ptr, require_device, stream_of
+from .hparam import hparam as hp
 
 M = 16            # SV_DIAR_M: eigenpairs of the subspace iteration, columns of the embedding
 MAX_N = 8192      # SV_DIAR_MAX_N
@@ -476,9 +483,364 @@ def cluster(dvectors, n_speakers=None, sigma=1.0, p=0.95, mult=0.01, k_min=1, k_
     return labels, info
 
 
-def diarize(net, files, precision="bf16", path=None, max_samples=2 ** 27, **kw):
+def diarize(net, files, precision="bf16", path=None, max_samples=2 ** 27, times=False, **kw):
     """dvector.embed_files followed by cluster, the d-vectors staying on the device in between:
     `files` is a list of (waveform, voiced ranges) as embed_files takes them; **kw goes to cluster.
-    Returns cluster's (labels, info): one label per aligned d-vector of every file."""
-    from .dvector import embed_files
-    return cluster(embed_files(net, files, precision=precision, path=path, max_samples=max_samples, on_device=True), **kw)
+    Returns cluster's (labels, info): one label per aligned d-vector of every file.  times=True
+    returns (labels, info, segments): per file the (start_s, end_s, label) list of segments() on the
+    file's dvector.aligned_spans -- their union is exactly the ranges embed_files kept."""
+    from .dvector import aligned_spans, embed_files
+    labels, info = cluster(embed_files(net, files, precision=precision, path=path, max_samples=max_samples,
+                                       on_device=True), **kw)
+    if not times:
+        return labels, info
+    return labels, info, segments(labels, [aligned_spans(ranges) for _, ranges in files])
+
+
+# ----------------------------------------------------------------------------- labels to wall-clock time
+def segments(labels, spans, sr=None):
+    """Per file the list of (start_s, end_s, label): every row (start_sample, end_sample, aligned_index)
+    of `spans` (dvector.aligned_spans) carries the label of its aligned d-vector; neighbouring spans
+    with one label and end == next start merge; times are sample / sr as Python floats."""
+    from .dvector import _sr
+    sr = _sr(sr)
+    if len(labels) != len(spans):
+        raise ValueError("segments: one label array and one span table per file")
+    out = []
+    for lab, sp in zip(labels, spans):
+        sp = np.asarray(sp, dtype=np.int64).reshape(-1, 3)
+        if sp.shape[0] and int(sp[:, 2].max()) >= len(lab):
+            raise ValueError(f"segments: spans name aligned d-vector {int(sp[:, 2].max())}, the file has {len(lab)} labels")
+        cur = []
+        for s, e, i in sp.tolist():
+            v = int(lab[i])
+            if cur and cur[-1][2] == v and cur[-1][1] == s:
+                cur[-1][1] = e
+            else:
+                cur.append([s, e, v])
+        out.append([(s / sr, e / sr, v) for s, e, v in cur])
+    return out
+
+
+def write_rttm(path, file_ids, segments):
+    """One `SPEAKER <file> 1 <tbeg> <tdur> <NA> <NA> <name> <NA> <NA>` line per segment (start_s, end_s,
+    speaker) of every file, files in order.  Times carry nine decimals, so read_rttm gives back the
+    sample positions (round(t * sr)) at any audio rate.  A file without segments gets a `;;` comment
+    line only: RTTM has no record for it."""
+    if len(file_ids) != len(segments):
+        raise ValueError("write_rttm: one id per file")
+    with open(path, "w") as f:
+        for fid, segs in zip(file_ids, segments):
+            fid = str(fid)
+            if not fid or any(c.isspace() for c in fid):
+                raise ValueError(f"write_rttm: file id {fid!r} is empty or holds white space")
+            if not segs:
+                f.write(f";; {fid} has no segments\n")
+            for s, e, spk in segs:
+                spk = str(spk)
+                if not spk or any(c.isspace() for c in spk):
+                    raise ValueError(f"write_rttm: speaker name {spk!r} is empty or holds white space")
+                f.write(f"SPEAKER {fid} 1 {float(s):.9f} {float(e) - float(s):.9f} <NA> <NA> {spk} <NA> <NA>\n")
+
+
+def read_rttm(path, file_ids=None):
+    """{file_id: [(start_s, end_s, speaker), ...]} of the SPEAKER lines of an RTTM file, in the file's
+    order (end = tbeg + tdur; speaker names are strings); every other line is skipped.  Ids in
+    `file_ids` get an entry even without a line."""
+    out = {str(fid): [] for fid in (file_ids or [])}
+    with open(path) as f:
+        for line in f:
+            p = line.split()
+            if len(p) < 8 or p[0] != "SPEAKER":
+                continue
+            t, d = float(p[3]), float(p[4])
+            out.setdefault(p[1], []).append((t, t + d, p[7]))
+    return out
+
+
+# ----------------------------------------------------------------------------- scoring: DER on a frame grid
+MAX_SPK = 32          # speakers per file and side: the bits of a frame's mask
+RASTER_PIECE = 2048   # split_rows: table rows longer than this many frames are cut (one wave per row)
+DER_OUT = 4 + MAX_SPK * MAX_SPK
+_MAX_FILES = 65535
+
+
+def split_rows(start, end, bits, file, step, piece=RASTER_PIECE):
+    """The segment table (start, end, bits, file) with every row longer than piece * step samples cut
+    into pieces of that length (the last one shorter): the same frames are covered, since every frame
+    centre of [s, e) lies in exactly one piece, and sv_seg_raster's one wave per row is an even load."""
+    start, end = np.asarray(start, dtype=np.int64), np.asarray(end, dtype=np.int64)
+    bits, file = np.asarray(bits, dtype=np.uint32), np.asarray(file, dtype=np.int64)
+    span = int(piece) * int(step)
+    n = np.maximum(1, -(-(end - start) // span))
+    if n.size == 0 or n.max() == 1:
+        return start, end, bits, file
+    row = np.repeat(np.arange(n.size), n)
+    k = np.arange(row.size) - np.repeat(np.cumsum(n) - n, n)
+    s = start[row] + k * span
+    return s, np.minimum(end[row], s + span), bits[row], file[row]
+
+
+def _scoring_device(device):
+    if device is None:
+        if not torch.cuda.is_available():
+            raise RuntimeError("pytorch_speaker_verification_amd ops run on the GPU only (HIP kernels, no CPU "
+                               "fallback) and no GPU is visible")
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"pytorch_speaker_verification_amd ops run on the GPU only (got device {device})")
+    return device
+
+
+def _int32_tensor(a, dev, name):
+    a = np.asarray(a)
+    if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+        raise ValueError(f"{name} needs 32 bits")
+    return torch.from_numpy(np.ascontiguousarray(a.astype(np.int64).astype(np.int32))).to(dev)
+
+
+def raster(seg_start, seg_end, seg_bits, seg_file, frame_off, step, mask=None, split=True, device=None, d_frame_off=None):
+    """Per-frame masks of a segment table (sv_seg_raster): mask[frame_off[f] + i] |= seg_bits[k] for
+    every frame i of file f = seg_file[k] whose centre i * step + step // 2 lies in [seg_start[k],
+    seg_end[k]) (samples), clamped to the file's own frames.  frame_off: host int [F + 1].  Returns the
+    int32 device tensor [frame_off[-1]] (the bits of a uint32); `mask` gives a tensor to OR into instead
+    (at least that long; words past frame_off[-1] are not touched).  split=False passes the rows as
+    they are, without split_rows.  d_frame_off: the int32 device copy of frame_off, where the caller
+    holds one (der uploads it once per batch)."""
+    frame_off = np.asarray(frame_off, dtype=np.int64).reshape(-1)
+    F, n_total = frame_off.size - 1, int(frame_off[-1])
+    if F < 1 or frame_off[0] != 0 or np.any(np.diff(frame_off) < 0) or n_total >= 2 ** 31:
+        raise ValueError("raster: frame_off must be ascending from 0, [F + 1] with F >= 1, below 2^31 frames")
+    if step < 1:
+        raise ValueError("raster: step must be >= 1")
+    dev = mask.device if mask is not None else _scoring_device(device)
+    if mask is None:
+        mask = torch.zeros(n_total, dtype=torch.int32, device=dev)
+    elif not mask.is_cuda or mask.dtype != torch.int32 or not mask.is_contiguous() or mask.numel() < n_total:
+        raise ValueError(f"raster: mask must be a contiguous int32 device tensor of at least {n_total} words")
+    rows = (np.asarray(seg_start, dtype=np.int64), np.asarray(seg_end, dtype=np.int64),
+            np.asarray(seg_bits, dtype=np.uint32), np.asarray(seg_file, dtype=np.int64))
+    if len({r.size for r in rows}) != 1:
+        raise ValueError("raster: the four segment tables must have one length")
+    if split:
+        rows = split_rows(*rows, step)
+    n_seg = int(rows[0].size)
+    if n_seg == 0 or n_total == 0:
+        return mask
+    with torch.cuda.device(dev):
+        d_s, d_e = _int32_tensor(rows[0], dev, "a segment start"), _int32_tensor(rows[1], dev, "a segment end")
+        d_b = torch.from_numpy(np.ascontiguousarray(rows[2]).view(np.int32)).to(dev)
+        d_f = _int32_tensor(np.clip(rows[3], -1, F), dev, "a file index")
+        d_off = torch.from_numpy(frame_off.astype(np.int32)).to(dev) if d_frame_off is None else d_frame_off
+        call("sv_seg_raster", ptr(d_s), ptr(d_e), ptr(d_b), ptr(d_f), n_seg, ptr(d_off), F, int(step), n_total,
+             ptr(mask), torch.cuda.current_stream(dev).cuda_stream)
+    return mask
+
+
+def count(ref, hyp, noscore, frame_off, uem=None, skip_overlap=False, d_frame_off=None):
+    """The integers of the DER per file (sv_der_count): uint64 numpy [F, 4 + 32 * 32] -- total, miss, fa,
+    both, then C[i][j] row-major -- over the scored frames of the int32 device masks ref, hyp, noscore
+    (and uem: frames with uem == 0 are not scored; None scores every frame) of raster().  d_frame_off
+    as in raster()."""
+    frame_off = np.asarray(frame_off, dtype=np.int64).reshape(-1)
+    F, n_total = frame_off.size - 1, int(frame_off[-1])
+    if F < 1 or F > _MAX_FILES or frame_off[0] != 0 or np.any(np.diff(frame_off) < 0) or n_total >= 2 ** 31:
+        raise ValueError(f"count: frame_off must be ascending from 0, [F + 1] with 1 <= F <= {_MAX_FILES}, below 2^31 frames")
+    for name, t in (("ref", ref), ("hyp", hyp), ("noscore", noscore), ("uem", uem)):
+        if t is None and name == "uem":
+            continue
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise RuntimeError("pytorch_speaker_verification_amd ops run on the GPU only "
+                               f"({name} is not a device tensor); build the masks with raster()")
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < n_total or t.device != ref.device:
+            raise ValueError(f"count: {name} must be a contiguous int32 tensor of at least {n_total} frames on ref's device")
+    dev = ref.device
+    with torch.cuda.device(dev):
+        out = torch.empty((F, DER_OUT), dtype=torch.int64, device=dev)
+        d_off = torch.from_numpy(frame_off.astype(np.int32)).to(dev) if d_frame_off is None else d_frame_off
+        call("sv_der_count", ptr(ref), ptr(hyp), ptr(noscore), ptr(uem), ptr(d_off), F, int(np.diff(frame_off).max()),
+             n_total, int(bool(skip_overlap)), ptr(out), torch.cuda.current_stream(dev).cuda_stream)
+        return out.cpu().numpy().view(np.uint64)
+
+
+def assignment(C):
+    """The one-to-one mapping of rows to columns of the integer matrix C [R, K] that maximises
+    sum_r C[r][col[r]] (the Hungarian method with potentials, exact in Python integers; min(R, K)
+    pairs): (col int64 [R], -1 for a row left out; the total)."""
+    C = np.asarray(C, dtype=np.int64)
+    if C.ndim != 2:
+        raise ValueError("assignment: C must be a matrix")
+    R, K = C.shape
+    if R == 0 or K == 0:
+        return np.full(R, -1, dtype=np.int64), 0
+    if R > K:
+        row_of, total = assignment(C.T)
+        col = np.full(R, -1, dtype=np.int64)
+        col[row_of] = np.arange(K)
+        return col, total
+    cost = (-C).tolist()
+    inf = 1 << 62
+    u, v, p, way = [0] * (R + 1), [0] * (K + 1), [0] * (K + 1), [0] * (K + 1)
+    for i in range(1, R + 1):
+        p[0], j0 = i, 0
+        minv, used = [inf] * (K + 1), [False] * (K + 1)
+        while True:
+            used[j0] = True
+            i0, delta, j1 = p[j0], inf, 0
+            row = cost[i0 - 1]
+            for j in range(1, K + 1):
+                if not used[j]:
+                    cur = row[j - 1] - u[i0] - v[j]
+                    if cur < minv[j]:
+                        minv[j], way[j] = cur, j0
+                    if minv[j] < delta:
+                        delta, j1 = minv[j], j
+            for j in range(K + 1):
+                if used[j]:
+                    u[p[j]] += delta
+                    v[j] -= delta
+                else:
+                    minv[j] -= delta
+            j0 = j1
+            if p[j0] == 0:
+                break
+        while j0:
+            j1 = way[j0]
+            p[j0] = p[j1]
+            j0 = j1
+    col = np.full(R, -1, dtype=np.int64)
+    for j in range(1, K + 1):
+        if p[j]:
+            col[p[j] - 1] = j - 1
+    return col, int(sum(int(C[r, c]) for r, c in enumerate(col)))
+
+
+def _positions(segs, n, sr, names, what):
+    """(start, end, bits) int lists of one file's (start_s, end_s, speaker) list: positions
+    int(round(t * sr)) clamped to [0, n]; speakers to bits by first appearance (names: filled in)."""
+    s_, e_, b_ = [], [], []
+    for t0, t1, spk in segs:
+        if spk not in names:
+            if len(names) >= MAX_SPK:
+                raise ValueError(f"der: more than {MAX_SPK} {what} speakers in one file")
+            names[spk] = len(names)
+        s_.append(min(max(int(round(t0 * sr)), 0), n))
+        e_.append(min(max(int(round(t1 * sr)), 0), n))
+        b_.append(1 << names[spk])
+    return s_, e_, b_
+
+
+def der(reference, hypothesis, n_samples, collar=0.25, skip_overlap=False, step=None, uem=None, sr=None,
+        max_frames=2 ** 27, device=None):
+    """The diarization error rate of per-file hypotheses against per-file references, both lists of
+    (start_s, end_s, speaker) per file, on a frame grid, for all files in one pass per batch on the GPU.
+
+    Grid: `step` samples per frame (default int(hp.data.hop * sr): 10 ms); a file of n_samples[f]
+    samples has ceil(n / step) frames; frame i has its centre at i * step + step // 2 and a segment
+    covers it iff start <= centre < end, with positions int(round(t * sr)) clamped to [0, n].  Around
+    every reference boundary t the frames of [t - c, t + c), c = round(collar * sr), are not scored;
+    `uem` (per file None or a list of (start_s, end_s) regions) restricts scoring to its regions;
+    skip_overlap leaves out frames with more than one reference speaker.  Over the scored frames, with
+    Nr / Nh the number of active reference / hypothesis speakers: total = sum Nr, miss = sum max(0,
+    Nr - Nh), fa = sum max(0, Nh - Nr); with the one-to-one speaker mapping that maximises the
+    co-occurrence sum_r C[r][map(r)] (assignment(), on the host), correct is that sum and
+    conf = sum min(Nr, Nh) - correct.  DER = (miss + fa + conf) / total in fp64.
+
+    Four sv_seg_raster launches (reference, hypothesis, collars, UEM) and one sv_der_count per batch of
+    files holding at most max_frames frames (a larger file alone).  Returns {"total", "miss", "fa",
+    "conf": int64 [F]; "file_der": float64 [F], nan where total == 0; "mapping": per file {reference
+    speaker: hypothesis speaker} for the mapped pairs that co-occur; "der": sum of errors / sum of total
+    over the files}.  More than 32 speakers on either side of a file is a ValueError.
+
+    This DER is quantised to `step`: a boundary moves to the next frame centre.  It is not claimed
+    equal to NIST md-eval's continuous-time figure, against which it has not been compared."""
+    from .dvector import _sr
+    sr = _sr(sr)
+    step = int(hp.data.hop * sr) if step is None else int(step)
+    if step < 1:
+        raise ValueError("der: step must be >= 1")
+    nfiles = len(reference)
+    if len(hypothesis) != nfiles or len(n_samples) != nfiles or (uem is not None and len(uem) != nfiles):
+        raise ValueError("der: reference, hypothesis, n_samples (and uem) need one entry per file")
+    ns = [int(n) for n in n_samples]
+    if nfiles and (min(ns) < 0 or max(ns) >= 2 ** 31):
+        raise ValueError("der: sample positions need 32 bits")
+    c = int(round(collar * sr))
+    if c < 0:
+        raise ValueError("der: collar must be >= 0")
+    frames = [-(-n // step) for n in ns]
+    # tables first (host): a speaker count above 32 is an error before anything runs
+    tabs = []
+    for f in range(nfiles):
+        rn, hn = {}, {}
+        rs, re_, rb = _positions(reference[f], ns[f], sr, rn, "reference")
+        hs, he, hb = _positions(hypothesis[f], ns[f], sr, hn, "hypothesis")
+        cs = [min(max(t - c, 0), ns[f]) for t in rs + re_] if c else []
+        ce = [min(max(t + c, 0), ns[f]) for t in rs + re_] if c else []
+        us = ue = None
+        if uem is not None:
+            us, ue = [0], [ns[f]]  # None: the whole file
+            if uem[f] is not None:
+                us = [min(max(int(round(t0 * sr)), 0), ns[f]) for t0, _ in uem[f]]
+                ue = [min(max(int(round(t1 * sr)), 0), ns[f]) for _, t1 in uem[f]]
+        tabs.append(((rs, re_, rb), (hs, he, hb), (cs, ce, [1] * len(cs)), None if us is None else (us, ue, [1] * len(us)),
+                     list(rn), list(hn)))
+    out = np.zeros((nfiles, DER_OUT), dtype=np.uint64)
+    dev = _scoring_device(device) if nfiles else None
+    groups = [g[i:i + _MAX_FILES] for g in _batches(frames, min(int(max_frames), 2 ** 31 - 1))
+              for i in range(0, len(g), _MAX_FILES)]
+    for ids in groups:
+        frame_off = np.concatenate([[0], np.cumsum([frames[i] for i in ids])])
+        if frame_off[-1] >= 2 ** 31:
+            raise ValueError("der: a file has 2^31 frames or more; raise step")
+        if frame_off[-1] == 0:
+            continue
+        d_off = torch.from_numpy(frame_off.astype(np.int32)).to(dev)  # one upload per batch
+        masks = []
+        for which in range(4):
+            if tabs[ids[0]][which] is None:
+                masks.append(None)
+                continue
+            rows = [tabs[i][which] for i in ids]
+            cols = [np.fromiter((v for r in rows for v in r[c]), dtype=np.int64) for c in range(3)]
+            cols.append(np.repeat(np.arange(len(ids)), [len(r[0]) for r in rows]))
+            masks.append(raster(*cols, frame_off, step, device=dev, d_frame_off=d_off))
+        out[ids] = count(masks[0], masks[1], masks[2], frame_off, uem=masks[3], skip_overlap=skip_overlap,
+                         d_frame_off=d_off)
+    res = {k: np.zeros(nfiles, dtype=np.int64) for k in ("total", "miss", "fa", "conf")}
+    res["file_der"] = np.full(nfiles, np.nan)
+    res["mapping"] = []
+    for f in range(nfiles):
+        rn, hn = tabs[f][4], tabs[f][5]
+        total, miss, fa, both = (int(v) for v in out[f, :4])
+        C = out[f, 4:].astype(np.int64).reshape(MAX_SPK, MAX_SPK)[:len(rn), :len(hn)]
+        col, correct = assignment(C)
+        res["total"][f], res["miss"][f], res["fa"][f], res["conf"][f] = total, miss, fa, both - correct
+        res["mapping"].append({rn[r]: hn[j] for r, j in enumerate(col.tolist()) if j >= 0 and C[r, j] > 0})
+        if total:
+            res["file_der"][f] = np.float64(miss + fa + both - correct) / np.float64(total)
+    err, tot = int(res["miss"].sum() + res["fa"].sum() + res["conf"].sum()), int(res["total"].sum())
+    res["der"] = float(np.float64(err) / np.float64(tot)) if tot else float("nan")
+    return res
+
+
+def evaluate(net, files, references, n_speakers=None, collar=0.25, skip_overlap=False, **kw):
+    """diarize(times=True) followed by der: `files` as diarize takes them, `references` per file a list
+    of (start_s, end_s, speaker).  n_speakers goes to cluster; "oracle" gives it each file's number of
+    reference speakers (a file with d-vectors and an empty reference gets 0, which cluster raises to
+    one speaker).  step, uem, sr, max_frames go to der, device to both, everything else in **kw
+    to diarize.  Returns der's dict plus "info", "labels" and "segments" of the diarization."""
+    if len(references) != len(files):
+        raise ValueError("evaluate: one reference per file")
+    der_kw = {k: kw.pop(k) for k in ("step", "uem", "sr", "max_frames") if k in kw}
+    if "device" in kw:
+        der_kw["device"] = kw["device"]
+    if isinstance(n_speakers, str):
+        if n_speakers != "oracle":
+            raise ValueError(f"evaluate: n_speakers must be None, an int, one entry per file or 'oracle' (got {n_speakers!r})")
+        n_speakers = [len({spk for _, _, spk in ref}) for ref in references]
+    labels, info, segs = diarize(net, files, times=True, n_speakers=n_speakers, **kw)
+    res = der(references, segs, [int(len(w)) for w, _ in files], collar=collar, skip_overlap=skip_overlap, **der_kw)
+    res.update(info=info, labels=labels, segments=segs)
+    return res

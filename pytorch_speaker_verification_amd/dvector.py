@@ -358,6 +358,43 @@ def batch_tables(frame_off, seg_file, n_files):
     return starts, part_off.astype(np.int32), [len(p) for p in parts]
 
 
+def aligned_spans(ranges, sr=None):
+    """Which samples every aligned d-vector of one file owns: int64 [n_spans, 3] rows (start_sample,
+    end_sample, aligned_index), from the file's voiced ranges alone (what embed_files takes).
+
+    The ranges embed_files keeps (1 + (b - a) // hop_n > WIN) have T = 1 + (b - a) // hop_n log-mel
+    frames and windows at the frames j of window_starts; the windows of all kept ranges, in order,
+    are numbered 0 .. n_win - 1 and partitions(n_win) gives each its aligned index.  The window at
+    frame j of range (a, b) owns the samples [a + j hop_n, a + (j + HOP) hop_n), the last window of
+    its range [a + j hop_n, b): a range's windows tile exactly [a, b).  Consecutive windows of one
+    range with one aligned index merge into one span.  Rows are ascending and disjoint, their union
+    is the kept ranges, and every aligned index 0 .. n_aligned - 1 (batch_tables' count) appears at
+    least once -- more than once where a partition straddles two ranges.  A file without a window
+    gives [0, 3]."""
+    hop_n = int(hp.data.hop * _sr(sr))
+    rg = np.asarray([(int(a), int(b)) for a, b in ranges], dtype=np.int64).reshape(-1, 2)
+    rg = rg[1 + (rg[:, 1] - rg[:, 0]) // hop_n > WIN]
+    if rg.shape[0] == 0:
+        return np.zeros((0, 3), dtype=np.int64)
+    a, b = rg[:, 0], rg[:, 1]
+    frame_off = np.concatenate([[0], np.cumsum(1 + (b - a) // hop_n)])
+    starts, counts = window_starts(frame_off)
+    counts = np.asarray(counts, dtype=np.int64)
+    rid = np.repeat(np.arange(rg.shape[0]), counts)           # the range of every window
+    j = starts.astype(np.int64) - frame_off[rid]              # its first frame within the range
+    s = a[rid] + j * hop_n
+    e = a[rid] + (j + HOP) * hop_n
+    last = np.cumsum(counts) - 1                              # (every kept range holds a window)
+    e[last] = b
+    parts = np.asarray(partitions(int(counts.sum())), dtype=np.int64)
+    idx = np.repeat(np.arange(parts.shape[0]), parts[:, 1] - parts[:, 0])
+    head = np.ones(s.size, dtype=bool)
+    head[1:] = (rid[1:] != rid[:-1]) | (idx[1:] != idx[:-1])
+    first = np.flatnonzero(head)
+    tail = np.concatenate([first[1:], [s.size]]) - 1
+    return np.stack([s[first], e[tail], idx[first]], axis=1)
+
+
 def _batches(sizes, max_samples):
     """Consecutive index groups whose sizes add up to at most max_samples (a larger item alone)."""
     groups, cur, tot = [], [], 0
